@@ -1,6 +1,7 @@
 """bench.py -- SNIPER training throughput on MI355X (BASELINE.json metric: train chips/s, 512x512, R101).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: DIR/<name>.npy)
 
 Workload (config.workload): BASELINE configs[1] -- ResNet-101 Faster-RCNN SNIPER, 3-scale chips,
 20 x 512 x 512 chips per GPU, fp16 storage / fp32 accumulate, seeded synthetic COCO-shaped data
@@ -706,6 +707,43 @@ def dist_probe(tr, step, sync, dist, world, reps=3):
 
 
 LINE_LIMIT = 4096      # bytes of the final JSON line (the driver keeps a tail of about 8 KB of stdout)
+DUMP_LIMIT = 64 << 20  # bytes of all arrays --dump-outputs writes
+PARAM_SAMPLE = 1024    # elements per parameter tensor in params_sample.npy
+
+
+def dump_outputs(path, lab, outs, output_names, arg_params):
+    """--dump-outputs: what the last timed step computed, as <name>.npy (floating point as float32, integers as float64,
+    both exact) -- the anchor labelling results (label_*), the network outputs (out_*) and, for the backward pass and the
+    SGD update, a fixed sample of the updated parameters (params_sample: per parameter in name order, PARAM_SAMPLE elements
+    drawn by a generator seeded from the name).  An array past the DUMP_LIMIT budget is replaced by a seeded sample of its
+    elements (<name>_sample).  Returns {file name: shape}."""
+    import re
+    import zlib
+
+    def seeded(name):
+        return np.random.default_rng(zlib.crc32(name.encode()))
+
+    arrays = [('label_' + k, v) for k, v in sorted(lab.items())]
+    arrays += [('out_' + n, o) for n, o in zip(output_names, outs)]
+    sample = []
+    for name in sorted(arg_params):
+        p = np.asarray(arg_params[name].asnumpy(), np.float32).reshape(-1)
+        idx = np.sort(seeded(name).choice(p.size, min(p.size, PARAM_SAMPLE), replace=False))
+        sample.append(p[idx])
+    arrays.append(('params_sample', np.concatenate(sample)))
+    os.makedirs(path, exist_ok=True)
+    left, written = DUMP_LIMIT, {}
+    for name, a in arrays:
+        a = a.asnumpy() if hasattr(a, 'asnumpy') else a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float32 if a.dtype.kind == 'f' else np.float64)
+        name = re.sub(r'[^A-Za-z0-9_.-]', '_', name)
+        if a.nbytes > left:
+            idx = np.sort(seeded(name).choice(a.size, left // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def _pick(d, keys):
@@ -782,7 +820,10 @@ def main():
     ap.add_argument('--no-inference', action='store_true', help='skip BASELINE config C5 (inf images/sec)')
     ap.add_argument('--no-fit-path', action='store_true', help='skip the reference main_train.py throughput leg (fit_path)')
     ap.add_argument('--no-c4', action='store_true', help='skip BASELINE config C4 (R-FCN head, 16 chips) at one GPU\'s share')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # the host driver only supports dmabuf IPC: without this RCCL's peer mapping fails with hipIpcGetMemHandle: invalid argument
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
@@ -816,8 +857,9 @@ def main():
         lab = anchors.assign(packed=packed[i % len(batches)], seed=i)
         label = [mx.nd.NDArray(lab['label']), mx.nd.NDArray(lab['bbox_target']), mx.nd.NDArray(lab['bbox_weight']),
                  mx.nd.NDArray(lab['gt_boxes'])]
-        tr.step(mx.io.DataBatch(data=b.data, label=label, pad=0, index=None, provide_data=b.provide_data,
-                                provide_label=b.provide_label))
+        outs = tr.step(mx.io.DataBatch(data=b.data, label=label, pad=0, index=None, provide_data=b.provide_data,
+                                       provide_label=b.provide_label))
+        return lab, outs
 
     def sync():
         torch.cuda.synchronize()
@@ -829,7 +871,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     host_dt = time.perf_counter() - t0     # host enqueue time: all launches issued, nothing waited for yet
     device = device_identity(local % torch.cuda.device_count())      # clocks sampled while the queued steps still run
     sync()
@@ -840,6 +882,10 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * args.batch * args.steps / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any further step: the network outputs are the executor's buffers, which the next step overwrites
+        dumped = dump_outputs(args.dump_outputs, last[0], last[1], tr.mod.output_names, tr.mod.get_params()[0])
 
     # ---- host cost of one step with an idle device: enqueue only, nothing waited for (host_dt above is throttled by the
     # launch queue once the host runs ahead of the device, so it is an upper bound, not the host's own time)
@@ -974,6 +1020,8 @@ def main():
             'library_sources_hash': library_sources_hash(),
             'roofline': roof, 'cpu_baseline': cpu,
         }
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if dist_report is not None:
             out['dist'] = dist_report
         if fit_path is not None:

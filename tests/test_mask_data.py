@@ -1,17 +1,18 @@
 """CPU: the mask branch's polygon plumbing (sniper_amd/data/mask_utils.py) against the REFERENCE's anchor_worker output
-(tests/golden/mask_polys_v1.npz, made by tests/golden/make_mask_golden.py) and, where the checkout is present, against
-lib/data_utils/mask_utils.py directly."""
+(tests/golden/mask_polys_v1.npz, made by tests/golden/make_mask_golden.py) and against lib/data_utils/mask_utils.py
+directly (tests/golden/mask_utils_v1.npz, made by tests/golden/make_mask_utils_golden.py)."""
 import os
 import sys
 
 import numpy as np
-import pytest
 
 from golden_util import anchor_case, golden
 from sniper_amd.data import mask_utils
 from sniper_amd.synthetic import make_roidb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, 'golden'))
+from make_mask_utils_golden import ENCODINGS, cases  # noqa: E402
 
 
 def test_encoded_polys_match_reference_anchor_worker():
@@ -36,20 +37,15 @@ def test_encoded_polys_match_reference_anchor_worker():
     assert rows > 150 and trunc > 0          # the 500-float budget truncated some objects
 
 
-@pytest.mark.ref
 def test_crop_and_encode_match_reference_mask_utils():
-    sys.path.insert(0, '/root/reference/lib/data_utils')
-    sys.dont_write_bytecode = True
-    import importlib
-    ref = importlib.import_module('mask_utils')
-    assert ref.__file__.startswith('/root/reference')
-    rs = np.random.RandomState(3)
-    roidb = make_roidb(4, seed=9, with_masks=True)
-    for r in roidb:
-        polys = r['gt_masks']
-        crop, scale = [float(rs.uniform(0, 100)), float(rs.uniform(0, 100)), 0, 0], float(rs.uniform(0.5, 3))
-        a, b = ref.crop_polys(polys, crop, scale), mask_utils.crop_polys(polys, crop, scale)
-        assert all(np.array_equal(x, y) and x.dtype == y.dtype for p, q in zip(a, b) for x, y in zip(p, q))
-        cats = rs.randint(0, 80, len(polys))
-        for mlen, mg in ((500, 100), (60, 3)):
-            assert np.array_equal(ref.poly_encoder(a, cats, mlen, mg), mask_utils.poly_encoder(b, cats, mlen, mg))
+    """lib/data_utils/mask_utils.py's crop_polys / poly_encoder on seeded polygons (tests/golden/mask_utils_v1.npz)."""
+    z = np.load(os.path.join(HERE, 'golden', 'mask_utils_v1.npz'))
+    for i, (polys, crop, scale, cats) in enumerate(cases()):
+        b = mask_utils.crop_polys(polys, crop, scale)
+        assert [len(p) for p in b] == z['nseg_%d' % i].tolist()
+        for j, p in enumerate(b):
+            for k, y in enumerate(p):
+                x = z['crop_%d_%d_%d' % (i, j, k)]
+                assert np.array_equal(x, y) and x.dtype == y.dtype, (i, j, k)
+        for mlen, mg in ENCODINGS:
+            assert np.array_equal(z['enc_%d_%d_%d' % (i, mlen, mg)], mask_utils.poly_encoder(b, cats, mlen, mg))

@@ -1,6 +1,8 @@
 """Graph-level checks (CPU): our network definitions build on the mx shim, infer the BASELINE shapes,
-and -- where the reference checkout is present -- have exactly the arguments / auxiliary states /
-outputs / shapes that the reference's own symbol file produces when run over the same shim."""
+and have exactly the arguments / auxiliary states / outputs / shapes / operator nodes that the reference's own
+symbol file produces when run over the same shim (tests/golden/symbols_v1.json.gz, generated from the reference
+itself by tests/golden/make_symbol_golden.py)."""
+import os
 import sys
 
 import numpy as np
@@ -8,6 +10,23 @@ import pytest
 
 from sniper_amd import config as cfgmod
 from sniper_amd.symbols.faster import resnet_mx_101_e2e as ours
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+from make_symbol_golden import B as B_GOLDEN, MNV2_DEFAULTS, R_DEFAULTS, graph_signature, load  # noqa: E402
+
+
+@pytest.fixture(scope='module')
+def symbols_golden():
+    return load()
+
+
+def _same_graph(got, want):
+    assert got['outputs'] == want['outputs']
+    assert got['arguments'] == want['arguments'] and got['aux_states'] == want['aux_states']
+    assert got['arg_shapes'] == want['arg_shapes'] and got['out_shapes'] == want['out_shapes']
+    assert got.get('aux_shapes') == want.get('aux_shapes')
+    # node-for-node: same operators with the same attributes (defaults dropped)
+    assert len(got['nodes']) == len(want['nodes']) and got['nodes'] == want['nodes']
 
 
 def _shapes(B, A=21, F=32, train=True):
@@ -59,47 +78,14 @@ def test_r101_test_and_rpn_graphs():
     assert rpn.list_outputs() == ['rpn_cls_prob_output', 'rpn_bbox_loss_output']
 
 
-@pytest.mark.ref
 @pytest.mark.parametrize('name', ['resnet_mx_101_e2e', 'resnet_mx_50_e2e'])
-def test_same_graph_as_reference_symbol_file(name):
-    import sniper_amd.mx as mx
-    mx.alias_as('mxnet')
-    for p in ('/root/reference', '/root/reference/lib', '/root/reference/symbols/faster'):
-        if p not in sys.path:
-            sys.path.insert(0, p)
+def test_same_graph_as_reference_symbol_file(symbols_golden, name):
     import importlib
-    sys.dont_write_bytecode = True
-    refmod = importlib.import_module(name)
     ourmod = importlib.import_module('sniper_amd.symbols.faster.' + name)
-    B = 2
     for train in (True, False):
-        cfg = _cfg(B)
-        a = getattr(refmod, name)(n_proposals=400, momentum=0.995, test_nbatch=B)
-        b = getattr(ourmod, name)(n_proposals=400, momentum=0.995, test_nbatch=B)
-        from sniper_amd.mx import symbol as _symmod
-        _symmod._counter().clear()          # auto-names (blockgrad0, _plus0, pooling0 ...) count per graph build
-        sa = a.get_symbol_rcnn(cfg, is_train=train)
-        _symmod._counter().clear()
-        sb = b.get_symbol_rcnn(cfg, is_train=train)
-        assert sa.list_outputs() == sb.list_outputs()
-        assert sorted(sa.list_arguments()) == sorted(sb.list_arguments())
-        assert sorted(sa.list_auxiliary_states()) == sorted(sb.list_auxiliary_states())
-        a.infer_shape(_shapes(B, train=train))
-        b.infer_shape(_shapes(B, train=train))
-        assert a.arg_shape_dict == b.arg_shape_dict and a.out_shape_dict == b.out_shape_dict
-        assert a.aux_shape_dict == b.aux_shape_dict
-        # node-for-node: same operators with the same attributes in the same topological order
-        dflt = {'dilate': '(1, 1)', 'stride': '(1, 1)', 'pad': '(0, 0)'}
-
-        def norm(n):
-            kv = [(k, str(tuple(v)) if isinstance(v, (list, tuple)) else str(v)) for k, v in n.attrs.items()
-                  if k not in ('workspace', 'cudnn_off')]
-            return (n.op, n.name, sorted((k, v) for k, v in kv if dflt.get(k) != v))
-
-        na = [norm(n) for n in sa._topo() if n.op]
-        nb = [norm(n) for n in sb._topo() if n.op]
-        assert len(na) == len(nb)
-        assert sorted(na) == sorted(nb)
+        want = symbols_golden['%s_%s' % (name, 'train' if train else 'test')]
+        b = getattr(ourmod, name)(n_proposals=400, momentum=0.995, test_nbatch=B_GOLDEN)
+        _same_graph(graph_signature(b, _cfg(B_GOLDEN), train, _shapes(B_GOLDEN, train=train), R_DEFAULTS), want)
 
 
 def _mnv2_shapes(B, train=True, A=15, F=16):
@@ -133,42 +119,14 @@ def test_mobilenetv2_graph_shapes():
                                 'chip_ids']
 
 
-@pytest.mark.ref
-def test_mobilenetv2_same_graph_as_reference_symbol_file():
-    import importlib
-    import sniper_amd.mx as mx
-    from sniper_amd.mx import symbol as _symmod
+def test_mobilenetv2_same_graph_as_reference_symbol_file(symbols_golden):
     from sniper_amd.symbols.faster import mobilenetv2_e2e as mn
-    mx.alias_as('mxnet')
-    for p in ('/root/reference', '/root/reference/lib', '/root/reference/symbols/faster'):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    sys.dont_write_bytecode = True
-    refmod = importlib.import_module('mobilenetv2_e2e')
-    B = 2
     for train in (True, False):
-        cfg = cfgmod.mobilenetv2_e2e(batch_images=B)
-        a, b = refmod.mobilenetv2_e2e(test_nbatch=B), mn.mobilenetv2_e2e(test_nbatch=B)
-        _symmod._counter().clear()
-        sa = a.get_symbol_rcnn(cfg, is_train=train)
-        _symmod._counter().clear()
-        sb = b.get_symbol_rcnn(cfg, is_train=train)
-        assert sa.list_outputs() == sb.list_outputs()
-        assert sorted(sa.list_arguments()) == sorted(sb.list_arguments())
-        assert sorted(sa.list_auxiliary_states()) == sorted(sb.list_auxiliary_states())
-        # the reference class never calls Symbol.__init__; infer through the base-class method all the same
-        a.infer_shape(_mnv2_shapes(B, train))
-        b.infer_shape(_mnv2_shapes(B, train))
-        assert a.arg_shape_dict == b.arg_shape_dict and a.out_shape_dict == b.out_shape_dict
-        dflt = {'dilate': '(1, 1)', 'stride': '(1, 1)', 'pad': '(0, 0)', 'num_group': '1'}
-
-        def norm(n):
-            kv = [(k, str(tuple(v)) if isinstance(v, (list, tuple)) else str(v)) for k, v in n.attrs.items()
-                  if k not in ('workspace', 'cudnn_off')]
-            return (n.op, n.name, sorted((k, v) for k, v in kv if dflt.get(k) != v))
-
-        na, nb = [norm(n) for n in sa._topo() if n.op], [norm(n) for n in sb._topo() if n.op]
-        assert len(na) == len(nb) and sorted(na) == sorted(nb)
+        want = symbols_golden['mobilenetv2_e2e_%s' % ('train' if train else 'test')]
+        cfg = cfgmod.mobilenetv2_e2e(batch_images=B_GOLDEN)
+        got = graph_signature(mn.mobilenetv2_e2e(test_nbatch=B_GOLDEN), cfg, train, _mnv2_shapes(B_GOLDEN, train), MNV2_DEFAULTS,
+                              aux_shapes=False)
+        _same_graph(got, want)
 
 
 def _mask_shapes(B, train=True, A=21, F=32):
@@ -199,43 +157,15 @@ def test_mask_graph_shapes():
     assert t.list_outputs() == ['rois_output', 'cls_prob_reshape_output', 'bbox_pred_reshape_output', 'im_ids', 'im_info', 'chip_ids']
 
 
-@pytest.mark.ref
 @pytest.mark.parametrize('autofocus', [False, True])
-def test_mask_same_graph_as_reference_symbol_file(autofocus):
-    import importlib
-    import sniper_amd.mx as mx
-    from sniper_amd.mx import symbol as _symmod
+def test_mask_same_graph_as_reference_symbol_file(symbols_golden, autofocus):
     from sniper_amd.symbols.faster import resnet_mx_101_e2e_mask as mk
-    mx.alias_as('mxnet')
-    for p in ('/root/reference', '/root/reference/lib', '/root/reference/symbols/faster'):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    sys.dont_write_bytecode = True
-    refmod = importlib.import_module('resnet_mx_101_e2e_mask')
-    B = 2
     for train in (True, False):
-        cfg = _cfg(B)
+        want = symbols_golden['resnet_mx_101_e2e_mask%s_%s' % ('_autofocus' if autofocus else '', 'train' if train else 'test')]
+        cfg = _cfg(B_GOLDEN)
         cfg.TRAIN.AUTO_FOCUS = cfg.TEST.AUTO_FOCUS = autofocus
-        a, b = refmod.resnet_mx_101_e2e_mask(momentum=0.995, test_nbatch=B), mk.resnet_mx_101_e2e_mask(momentum=0.995, test_nbatch=B)
-        _symmod._counter().clear()
-        sa = a.get_symbol_rcnn(cfg, is_train=train)
-        _symmod._counter().clear()
-        sb = b.get_symbol_rcnn(cfg, is_train=train)
-        assert sa.list_outputs() == sb.list_outputs()
-        assert sorted(sa.list_arguments()) == sorted(sb.list_arguments())
-        assert sorted(sa.list_auxiliary_states()) == sorted(sb.list_auxiliary_states())
-        shp = _mask_shapes(B, train)
+        shp = _mask_shapes(B_GOLDEN, train)
         if autofocus and train:
-            shp['scale_label'] = (B, 1024)
-        a.infer_shape(shp)
-        b.infer_shape(shp)
-        assert a.arg_shape_dict == b.arg_shape_dict and a.out_shape_dict == b.out_shape_dict
-        dflt = {'dilate': '(1, 1)', 'stride': '(1, 1)', 'pad': '(0, 0)'}
-
-        def norm(n):
-            kv = [(k, str(tuple(v)) if isinstance(v, (list, tuple)) else str(v)) for k, v in n.attrs.items()
-                  if k not in ('workspace', 'cudnn_off')]
-            return (n.op, n.name, sorted((k, v) for k, v in kv if dflt.get(k) != v))
-
-        na, nb = [norm(n) for n in sa._topo() if n.op], [norm(n) for n in sb._topo() if n.op]
-        assert len(na) == len(nb) and sorted(na) == sorted(nb)
+            shp['scale_label'] = (B_GOLDEN, 1024)
+        got = graph_signature(mk.resnet_mx_101_e2e_mask(momentum=0.995, test_nbatch=B_GOLDEN), cfg, train, shp, R_DEFAULTS, aux_shapes=False)
+        _same_graph(got, want)
