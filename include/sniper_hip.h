@@ -35,10 +35,11 @@ enum { SN_OK = 0, SN_ERR_ARG = 1, SN_ERR_HIP = 2, SN_ERR_WORKSPACE = 3, SN_ERR_U
 /* Library / device sanity. */
 int sn_version(void);
 const char *sn_last_error(void); /* thread-local text of the last failure */
-/* Test / A-B switch (process-wide, atomic; no reference counterpart): "proposal_full_sort" = 1 orders the proposals with the
+/* Test switch (process-wide, atomic; no reference counterpart): "proposal_full_sort" = 1 orders the proposals with the
  * general global-memory bitonic sort instead of radix select + LDS sort, "nms_full_mask" = 1 runs the full bitmask + scan
- * instead of the lazy kernel.  Results are identical either way (that is what the tests use it for; environment spellings, read
- * once at load: SNIPER_FULL_SORT, SNIPER_NMS_FULL). */
+ * instead of the lazy kernel, "conv_no_persist" = 1 gives every convolution workgroup one output tile (no persistent tile loop).  Results are
+ * identical either way (that is what the tests use it for; environment spellings, read once at load: SNIPER_FULL_SORT,
+ * SNIPER_NMS_FULL, SNIPER_CONV_NO_PERSIST).  Any other name is an error. */
 int sn_debug_option(const char *name, int value);
 
 /* ------------------------------------------------------------------ box geometry ------------- */
@@ -323,12 +324,8 @@ int sn_bn_global_scale_shift(const float *gamma, const float *beta, const float 
                              float *scale, float *shift, sn_stream_t stream);
 int sn_bn_apply(const void *x, void *y, int M, int C, int ps_in, int ps_out, const float *scale, const float *shift, int relu,
                 sn_stream_t stream); /* relu: 0 none, 1 ReLU, 2 ReLU6 = clip(0,6); same code in sn_bn_backward */
-/* sn_bn_finalize_blocks + sn_bn_apply, optionally in ONE launch: with few partial rows (nblk <= 160, C % 64 == 0 -- the convolution row tiles
- * of a 20-chip stage-3 / stage-4 map) every applying workgroup owns a 64-channel slab and reduces the slab's partials itself, in
- * sn_bn_finalize_blocks' summation order (same scale / shift / saved statistics / moving averages, bit for bit); otherwise the two
- * launches.  sn_bn_backward_blocks folds its finalize into the dx pass under the same condition.
- * OPT-IN: sn_debug_option("bn_fused_finalize", 1) (SNIPER_BN_FUSED_FINALIZE); by default both entries issue the separate launches --
- * in the training step the fused form measured 1.1 ms per step SLOWER (profiles/r06_ab_bn_fused.txt). */
+/* sn_bn_finalize_blocks + sn_bn_apply (two launches); sn_bn_backward_blocks likewise issues its finalize, then the dx pass.
+ * (Folding the finalize into the applying pass measured 1.1 ms per step slower, profiles/r06_ab_bn_fused.txt, and was removed.) */
 int sn_bn_apply_blocks(const float *partials, int nblk, const void *x, void *y, int M, int C, int ps_in, int ps_out, float eps,
                        float momentum, const float *gamma, const float *beta, float *run_mean, float *run_var, float *scale,
                        float *shift, float *save_mean, float *save_invstd, int relu, sn_stream_t stream);
@@ -415,9 +412,8 @@ int sn_pick_bwd(const void *dy, const float *index, void *dx, int N, int HW, int
  * OVERWRITTEN (every element written exactly once, no atomics); ws = sn_dpsroi_bwd_workspace_bytes(R). */
 int sn_dpsroi_pool_fwd(const void *data, const float *rois, const float *trans, void *out, int R, int H, int W, int C, int pooled,
                        int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream);
-/* ... with the number of images B of `data` (every RoI's image index in [0, B)).  OPT-IN sn_debug_option("dpsroi_slab", 1) /
- * SNIPER_DPSROI_SLAB: the (image, 64-channel slab)-stationary kernel (maps of <= 1024 cells, C % 64 == 0, <= 49 bins) -- same outputs
- * bit for bit, measured 1.6x SLOWER at R = 6000 (the bin geometry is recomputed per slab: profiles/r06_kab_dpsroi.txt). */
+/* ... with the number of images B of `data` (every RoI's image index in [0, B)): the same launch.  (An (image, 64-channel
+ * slab)-stationary kernel behind it measured 1.6x slower at R = 6000, profiles/r06_kab_dpsroi.txt, and was removed.) */
 int sn_dpsroi_pool_fwd_images(const void *data, const float *rois, const float *trans, void *out, int R, int B, int H, int W, int C,
                               int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream);
 size_t sn_dpsroi_bwd_workspace_bytes(int R);

@@ -279,16 +279,12 @@ __global__ __launch_bounds__(64 * (WMW * WNW + (PS ? 4 : 0)), MINW) void conv_dm
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(xb) + cbo, 0, (int)(p.x_bytes - cbo), 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wb) + wbo, 0, (int)(p.w_bytes - wbo), 0x00020000);
     half_t *const sa = lds + buf * STAGE, *const sb = b_lds + buf * STAGE;
-    if (!(PS && (p.probe & 1) && (g_kh != kh0 || g_kw != kw0))) {      // (ConvParams::probe: timing probe, normally 0)
 #pragma unroll
-      for (int i = 0; i < AGW; ++i)
-        dma16(rx, sa + a_grp[i] * 512, a_voff[i]);
-    }
-    if (!(PS && (p.probe & 2) && (g_kh != kh0 || g_kw != kw0 || g_kc != 0))) {      // (bit 1: the weight pieces of every K-step but the first)
+    for (int i = 0; i < AGW; ++i)
+      dma16(rx, sa + a_grp[i] * 512, a_voff[i]);
 #pragma unroll
-      for (int i = 0; i < BGW; ++i)
-        dma16(rw, sb + b_grp[i] * 512, w_voff[i]);
-    }
+    for (int i = 0; i < BGW; ++i)
+      dma16(rw, sb + b_grp[i] * 512, w_voff[i]);
     if constexpr (PERSIST) {
       ++g_kc;      // (one tap: fetch_seek re-positions at the tile boundary)
     } else if (++g_kc == kpt) {
@@ -398,7 +394,7 @@ __global__ __launch_bounds__(64 * (WMW * WNW + (PS ? 4 : 0)), MINW) void conv_dm
         if (S > 3 && young >= 2) wait_vmcnt<(S > 3 ? 2 : 0) * L>();
         else if (S > 2 && young == 1) wait_vmcnt<(S > 2 ? 1 : 0) * L>();
         else wait_vmcnt<0>();
-        if (!(p.probe & 4)) __builtin_amdgcn_s_barrier();      // (probe bit 2: the K loop without its step barrier -- timing only)
+        __builtin_amdgcn_s_barrier();
         if (t + S - 1 < nk) issue(nxt);
         nxt = nxt + 1 == S ? 0 : nxt + 1;
       }
@@ -433,7 +429,7 @@ __global__ __launch_bounds__(64 * (WMW * WNW + (PS ? 4 : 0)), MINW) void conv_dm
       };
       auto step_barrier = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every fragment read of the stage behind this barrier has returned
-        if (!(p.probe & 4)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
       };
       if (nk > 0) {
         step_barrier();
@@ -904,8 +900,6 @@ int conv_dma_launch(const ConvParams &p, bool dgrad, int cfg, hipStream_t s) {
   if (trace) {
     ConvParams q = p;
     q.trace = trace;
-    static const int probe = getenv("SNIPER_CONV_PROBE_SKIP_A") ? atoi(getenv("SNIPER_CONV_PROBE_SKIP_A")) : 0;
-    q.probe = probe;
     return dgrad ? launch_cfg<true>(q, cfg, s) : launch_cfg<false>(q, cfg, s);
   }
   return dgrad ? launch_cfg<true>(p, cfg, s) : launch_cfg<false>(p, cfg, s);

@@ -303,132 +303,6 @@ __global__ __launch_bounds__(512) void dpsroi_fwd_roi_kernel(const half_t *__res
   }
 }
 
-// ---- (image, 64-channel slab)-stationary forward (round 6) ------------------------------------------------
-// The per-RoI kernel above gathers every window cell through TCP / L2: 49 bins x ~9 cells x 512 B = 226 KB per RoI, 1.35 GB per call
-// at R = 6000 for a 10.5 MB map and 150 MB of output -- the call is bound by cache gather bandwidth (8.7 TB/s over its 155 us), not
-// by HBM.  Here a workgroup owns one image's 64-channel slab for the whole launch: H x W x 64 fp16 (128 KB at 32 x 32) arrives in
-// LDS once by LDS-DMA, and the workgroup walks the image's RoIs (every T-th of them: T workgroups share a slab so that the
-// B x C/64 x T grid fills the chip), twelve at a time: one thread per (RoI, bin) puts the separable window weights into LDS, then
-// the threads walk the (RoI, bin, 16-byte chunk) items with ds_read_b128 gathers.  Same bin geometry, same cell order, same
-// products as dpsroi_fwd_roi_kernel: identical outputs.  Maps beyond 1024 cells (test-time images), C % 64 != 0 or more than 49
-// bins take the per-RoI kernel.  RoIs whose image index lies outside [0, B) are not written (the per-RoI kernel would read out of
-// bounds for them).
-typedef __attribute__((address_space(3))) void *roi_lds_ptr_t;
-constexpr int kSlabC = 64, kSlabPix = 1024, kSlabRois = 12, kSlabThreads = 1024, kSlabBins = 49;
-struct BinWin4 {
-  float wx[4], wy[4];
-  int geo;          // x_lo | y_lo << 11 | nx << 22 | ny << 26 | slow << 30 (slow: a window beyond 4 cells per axis -> weights on the fly)
-  float inv;
-};
-template <int SM>
-__global__ __launch_bounds__(kSlabThreads) void dpsroi_fwd_slab_kernel(const half_t *__restrict__ data, const float *__restrict__ rois,
-                                                                       const float *__restrict__ trans, half_t *__restrict__ out, int R,
-                                                                       int H, int W, int C, int P, int S, float scale, float trans_std,
-                                                                       int T) {
-  __shared__ __attribute__((aligned(1024))) half_t slab[kSlabPix * kSlabC];
-  __shared__ BinWin4 win[kSlabRois * kSlabBins];
-  __shared__ int list[kSlabThreads];
-  __shared__ int s_n;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nslab = C / kSlabC, nb = P * P, npix = H * W;
-  const int t = blockIdx.x % T, bs = blockIdx.x / T, sl = bs % nslab, b = bs / nslab;
-  // ---- the slab: pixel p's 128 bytes at slab + 64 p; one LDS-DMA instruction moves 8 pixels (lane l: pixel l >> 3, chunk l & 7)
-  {
-    const half_t *img = data + (size_t)b * npix * C + sl * kSlabC;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t *>(img), 0, (int)(((size_t)(npix - 1) * C + kSlabC) * 2), 0x00020000);
-    for (int piece = wave; piece * 8 < npix; piece += kSlabThreads / 64) {
-      const int pix = piece * 8 + (lane >> 3);
-      const unsigned voff = pix < npix ? (unsigned)pix * (unsigned)C * 2u + (unsigned)(lane & 7) * 16u : 0xFFFFFF00u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (roi_lds_ptr_t)(slab + piece * 512), 16, voff, 0, 0, 0);
-    }
-  }
-  const int cand = (R - t + T - 1) / T;        // this workgroup's candidates: r = t + T k
-  for (int base = 0; base < cand; base += kSlabThreads) {
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    {
-      const int k = base + tid, r = t + T * k;
-      if (k < cand && (int)rois[(size_t)r * 5] == b) list[atomicAdd(&s_n, 1)] = r;      // (any order: the rows are independent)
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the slab has landed (first pass)
-    __syncthreads();
-    const int n = s_n;
-    for (int j0 = 0; j0 < n; j0 += kSlabRois) {
-      const int nr = min(kSlabRois, n - j0);
-      if (tid < nr * nb) {
-        const int j = tid / nb, bin = tid - j * nb, r = list[j0 + j];
-        const int ph = bin / P, pw = bin - ph * P;
-        const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-        const AxisSamplesT<SM> ax = axis_samples<SM>(g.wstart, g.sub_w, S, W), ay = axis_samples<SM>(g.hstart, g.sub_h, S, H);
-        BinWin4 &bw = win[tid];
-        const int count = ax.n * ay.n;
-        const int nx = count ? ax.hi - ax.lo + 1 : 0, ny = count ? ay.hi - ay.lo + 1 : 0;
-        const int slow = (nx > 4 || ny > 4) ? 1 : 0;
-        bw.inv = count ? 1.f / (float)count : 0.f;
-        bw.geo = ax.lo | (ay.lo << 11) | (min(nx, 15) << 22) | (min(ny, 15) << 26) | (slow << 30);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          bw.wx[k] = (!slow && k < nx) ? tent_sum(ax, ax.lo + k) : 0.f;
-          bw.wy[k] = (!slow && k < ny) ? tent_sum(ay, ay.lo + k) : 0.f;
-        }
-      }
-      __syncthreads();
-      for (int it = tid; it < nr * nb * 8; it += kSlabThreads) {
-        const int j = it / (nb * 8), rem = it - j * nb * 8, bin = rem >> 3, chunk = rem & 7;
-        const int r = list[j0 + j];
-        const BinWin4 &bw = win[j * nb + bin];
-        const int geo = bw.geo;
-        const int x_lo = geo & 2047, y_lo = (geo >> 11) & 2047, nx = (geo >> 22) & 15, ny = (geo >> 26) & 15, slow = (geo >> 30) & 1;
-        float sum[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) sum[q] = 0.f;
-        const half_t *img = slab + chunk * 8;
-        if (!slow && nx > 0) {
-          const half_t *wbase = img + (y_lo * W + x_lo) * kSlabC;
-          auto window = [&](auto n_tag) {
-            constexpr int NW = decltype(n_tag)::value;
-            half8 v[NW][NW];
-#pragma unroll
-            for (int ky = 0; ky < NW; ++ky)
-#pragma unroll
-              for (int kx = 0; kx < NW; ++kx) v[ky][kx] = *reinterpret_cast<const half8 *>(wbase + (min(ky, ny - 1) * W + min(kx, nx - 1)) * kSlabC);
-#pragma unroll
-            for (int ky = 0; ky < NW; ++ky)
-#pragma unroll
-              for (int kx = 0; kx < NW; ++kx) {
-                const float wgt = bw.wy[ky] * bw.wx[kx];      // zero beyond (ny, nx)
-                fma_mix8(sum, wgt, v[ky][kx]);
-              }
-          };
-          if (nx <= 2 && ny <= 2) window(std::integral_constant<int, 2>{});
-          else if (nx <= 3 && ny <= 3) window(std::integral_constant<int, 3>{});
-          else window(std::integral_constant<int, 4>{});
-        } else if (slow) {     // a window beyond 4 cells per axis: weights on the fly, as dpsroi_fwd_kernel
-          const int ph = bin / P, pw = bin - ph * P;
-          const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-          const AxisSamplesT<SM> ax = axis_samples<SM>(g.wstart, g.sub_w, S, W), ay = axis_samples<SM>(g.hstart, g.sub_h, S, H);
-          for (int y = ay.lo; y <= ay.hi; ++y) {
-            const float wy = tent_sum(ay, y);
-            if (wy == 0.f) continue;
-            for (int x = ax.lo; x <= ax.hi; ++x) {
-              const float wgt = wy * tent_sum(ax, x);
-              if (wgt == 0.f) continue;
-              const half8 v = *reinterpret_cast<const half8 *>(img + (y * W + x) * kSlabC);
-#pragma unroll
-              for (int q = 0; q < 8; ++q) sum[q] += wgt * (float)v[q];
-            }
-          }
-        }
-        half8 o;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) o[q] = (half_t)(sum[q] * bw.inv);
-        *reinterpret_cast<half8 *>(out + ((size_t)r * nb + bin) * C + sl * kSlabC + chunk * 8) = o;
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // Backward.  The data gradient is a scatter of R*P*P*S*S*4 bilinear corners; instead of 4.8 G global atomics
 // (v1: 138 ms at R=6000) the feature map is cut into 4x4-cell tiles and each workgroup OWNS one tile of one image
 // for 256 channels (one channel per thread, 16 fp32 accumulators in registers, written exactly once -> no zeroing,
@@ -964,33 +838,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   }
 }
 
-// workgroup size of the per-RoI kernels (threads; a multiple of 64, >= the bin count): A/B knob, read once at load time
-static const int kRoiBlock = [] {
-  const char *v = getenv("SNIPER_DPSROI_BLOCK");
-  const int b = v && *v ? atoi(v) : 256;
-  return (b == 64 || b == 128 || b == 256 || b == 512) ? b : 256;
-}();
+// workgroup size of the per-RoI kernels (threads; a multiple of 64, >= the bin count; 64, 128 and 512 were slower,
+// profiles/r06_kab_dpsroi_block.txt)
+constexpr int kRoiBlock = 256;
 static long blocks_for(long total) {
   long b = (total + 255) / 256;
   return b < 1 ? 1 : (b > 16384 ? 16384 : b);
 }
 
-static int dpsroi_fwd_launch(const void *data, const float *rois, const float *trans, void *out, int R, int B, int H, int W, int C,
-                             int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream) {
+SN_EXPORT int sn_dpsroi_pool_fwd(const void *data, const float *rois, const float *trans, void *out, int R, int H, int W, int C,
+                                 int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream) {
   SN_REQUIRE(data && rois && out && R > 0 && C % 8 == 0 && pooled > 0 && sample_per_part > 0 && sample_per_part <= kMaxS,
              "sn_dpsroi_pool_fwd: bad arguments (sample_per_part <= %d)", kMaxS);
-  // the slab-stationary kernel where the map fits (training chips) and the RoIs are many enough to amortise a slab load per workgroup
-  if (B > 0 && H * W <= kSlabPix && C % kSlabC == 0 && pooled * pooled <= kSlabBins && R >= 8 * B &&
-      (size_t)H * W * C * 2 < 0xFFFFFF00ul && sn_debug_get(SN_OPT_DPSROI_SLAB) != 0) {
-    const int wgs = B * (C / kSlabC);
-    const int T = wgs >= 256 ? 1 : (256 / wgs > 8 ? 8 : 256 / wgs);
-    if (sample_per_part <= 4)
-      hipLaunchKernelGGL(dpsroi_fwd_slab_kernel<4>, dim3((unsigned)(wgs * T)), dim3(kSlabThreads), 0, sn_stream(stream), (const half_t *)data,
-                         rois, trans, (half_t *)out, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std, T);
-    else
-      hipLaunchKernelGGL(dpsroi_fwd_slab_kernel<kMaxS>, dim3((unsigned)(wgs * T)), dim3(kSlabThreads), 0, sn_stream(stream), (const half_t *)data,
-                         rois, trans, (half_t *)out, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std, T);
-  } else if (pooled * pooled <= kBinsMax && sample_per_part <= 4)
+  if (pooled * pooled <= kBinsMax && sample_per_part <= 4)
     hipLaunchKernelGGL(dpsroi_fwd_roi_kernel<4>, dim3((unsigned)R), dim3(kRoiBlock), 0, sn_stream(stream), (const half_t *)data, rois, trans,
                        (half_t *)out, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std);
   else if (pooled * pooled <= kBinsMax)
@@ -1004,16 +864,11 @@ static int dpsroi_fwd_launch(const void *data, const float *rois, const float *t
   return SN_OK;
 }
 
-SN_EXPORT int sn_dpsroi_pool_fwd(const void *data, const float *rois, const float *trans, void *out, int R, int H, int W, int C,
-                                 int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream) {
-  return dpsroi_fwd_launch(data, rois, trans, out, R, 0, H, W, C, pooled, sample_per_part, spatial_scale, trans_std, stream);
-}
-
-// the same with the number of images B of `data` (every RoI's image index in [0, B)): lets the launch take the slab-stationary kernel
+// the same with the number of images B of `data` (every RoI's image index in [0, B)): the same launch
 SN_EXPORT int sn_dpsroi_pool_fwd_images(const void *data, const float *rois, const float *trans, void *out, int R, int B, int H, int W,
                                         int C, int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream) {
   SN_REQUIRE(B > 0, "sn_dpsroi_pool_fwd_images: B = %d", B);
-  return dpsroi_fwd_launch(data, rois, trans, out, R, B, H, W, C, pooled, sample_per_part, spatial_scale, trans_std, stream);
+  return sn_dpsroi_pool_fwd(data, rois, trans, out, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std, stream);
 }
 
 SN_EXPORT size_t sn_dpsroi_bwd_workspace_bytes(int R) { return sn_align(sizeof(int4) * (size_t)(R > 0 ? R : 1)); }

@@ -715,7 +715,7 @@ class Executor(object):
         everything from them (fp16 copies, BatchNorm scale / shift, BatchNorm-folded weights: Module._exe_for): nothing to compute --
         round 5 re-ran ~340 copies, 101 scale / shift kernels and 64 folds per new shape, 6 ms of host time each.  False = something
         is not there yet (the caller refreshes as before)."""
-        if self.for_training or not self.fold_store.get('__valid__') or os.environ.get('SNIPER_ADOPT_DERIVED', '1') == '0':
+        if self.for_training or not self.fold_store.get('__valid__'):
             return False
         if not all(n in self.shared_names for n in list(self.params) + list(self.aux)):
             return False
@@ -846,22 +846,17 @@ class Executor(object):
                     # on entry -- most of the 6 - 39 ms a capture cost per new batch shape (tools/cold_shape_probe.py).  The eager
                     # first call already made every lazy allocation, so nothing here needs freed memory.
                     g = torch.cuda.CUDAGraph()
-                    if os.environ.get('SNIPER_INFER_LIGHT_CAPTURE', '1') == '0':      # (A/B: the torch context, as until round 5)
-                        torch.cuda.synchronize()
-                        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                    cur = torch.cuda.current_stream()
+                    side = self.__dict__.setdefault('_capture_stream', None) or torch.cuda.Stream(device=self.device)
+                    self._capture_stream = side
+                    side.wait_stream(cur)
+                    with torch.cuda.stream(side):
+                        g.capture_begin(capture_error_mode='thread_local')
+                        try:
                             self._forward_body()
-                    else:
-                        cur = torch.cuda.current_stream()
-                        side = self.__dict__.setdefault('_capture_stream', None) or torch.cuda.Stream(device=self.device)
-                        self._capture_stream = side
-                        side.wait_stream(cur)
-                        with torch.cuda.stream(side):
-                            g.capture_begin(capture_error_mode='thread_local')
-                            try:
-                                self._forward_body()
-                            finally:
-                                g.capture_end()
-                        cur.wait_stream(side)
+                        finally:
+                            g.capture_end()
+                    cur.wait_stream(side)
                     g.replay()
                     self._infer_graph = g
                     if gc_was:

@@ -504,7 +504,7 @@ class ConvolutionStep(_GemmLike):
         return (self.N, self.H, self.W, self.C)
 
     def _stats_blocks(self):
-        if self.is_stem or self.depthwise or self.out_f32 or os.environ.get('SNIPER_FUSE_BN_STATS', '1') == '0':
+        if self.is_stem or self.depthwise or self.out_f32:
             return 0
         res = getattr(self, 'fused_residual', None)
         return hip.query('sn_conv_fwd_stats_blocks', self.N, self.H, self.W, self.C, self.C, self.O, self.O,
@@ -578,8 +578,7 @@ class ConvolutionStep(_GemmLike):
             # test-time launches with far fewer output tiles than CUs (batches of two FocusChips): contraction split over copies
             # of the tile grid (sn_conv_fwd_splitk; the query is 0 for every layer that would not be split)
             if getattr(self, '_splitk_bytes', None) is None:
-                self._splitk_bytes = 0 if os.environ.get('SNIPER_CONV_SPLITK', '1') == '0' else \
-                    int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
+                self._splitk_bytes = int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
             dual = getattr(self, 'dual_bn', None)
             if dual is not None and not ex.is_train:
                 # the next unit's BatchNorm + ReLU as the epilogue's second output (BatchNormStep.setup), split-K or not
@@ -621,9 +620,8 @@ class ConvolutionStep(_GemmLike):
         """The batch-statistics BatchNorm whose (activated) output is this convolution's input and nobody else's: the data
         gradient written here is then its complete dL/dy, and the epilogue can carry the backward reduction.
         On by default since the epilogue reads the BatchNorm input 16 bytes per lane, prefetched before the K loop, with the
-        per-channel constants hoisted (27.29 -> 26.98 ms per step, same box; with the earlier 8-byte epilogue it cost 1.5 %).
-        SNIPER_FUSE_BN_BWD=0 restores the separate reduction pass."""
-        if acc is not None or os.environ.get('SNIPER_FUSE_BN_BWD', '1') != '1' or self.x.fmt != 'act':
+        per-channel constants hoisted (27.29 -> 26.98 ms per step, same box; with the earlier 8-byte epilogue it cost 1.5 %)."""
+        if acc is not None or self.x.fmt != 'act':
             return None
         bn = self.x.producer
         if type(bn).__name__ != 'BatchNormStep' or bn.sole_consumer is not self.node or bn.global_stats or bn.is_stem:
@@ -658,8 +656,7 @@ def _fwd_splitk(step, x, w, bias, dst, geom):
         return False
     nbytes = getattr(step, '_splitk_bytes', None)
     if nbytes is None:
-        nbytes = step._splitk_bytes = 0 if '0' in (os.environ.get('SNIPER_CONV_SPLITK', '1'), os.environ.get('SNIPER_FC_SPLITK', '1')) else \
-            int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
+        nbytes = step._splitk_bytes = int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
     if not nbytes:
         return False
     if getattr(step, 'out_f32', False):
@@ -920,8 +917,7 @@ class BinaryStep(Step):
             st = me.producer
             cons = ex.consumers.get((id(st.node), 0), []) if st is not None else []
             if (type(st).__name__ == 'ConvolutionStep' and not st.depthwise and not st.is_stem and not st.out_f32 and
-                    len(cons) == 1 and getattr(st, 'fused_residual', None) is None and me is not other and
-                    os.environ.get('SNIPER_FUSE_RESIDUAL', '1') != '0'):
+                    len(cons) == 1 and getattr(st, 'fused_residual', None) is None and me is not other):
                 st.fused_residual, st.fused_dst = other, self.y
                 self.fused_conv = st
 
@@ -1329,7 +1325,7 @@ class DPSROIPoolStep(Step):
         # (Param.out_perm; reference order at the checkpoint boundary as ever) -- and the pooling kernels index (gh*G + gw)*D + d.
         self.gm = 0
         prod = self.x.producer
-        if (self.G > 1 and os.environ.get('SNIPER_PS_GROUP_MAJOR', '1') != '0' and type(prod).__name__ == 'ConvolutionStep'
+        if (self.G > 1 and type(prod).__name__ == 'ConvolutionStep'
                 and self.x.fmt == 'act' and not prod.depthwise and not prod.out_f32 and getattr(prod, 'fold_bn', None) is None
                 and len(ex.consumers.get((id(prod.node), 0), [])) == 1 and (id(prod.node), 0) not in ex.head_keys):
             G, D = self.G, self.D

@@ -89,9 +89,9 @@ _TLS = None
 
 def _worker_stream():
     """This thread's own stream when it is NOT the main thread, has a GPU bound and still sits on the default stream (a thread that
-    already switched streams -- sniper_amd's PrefetchingIter worker -- keeps its own).  SNIPER_PREFETCH_STREAM=0: never."""
+    already switched streams -- sniper_amd's PrefetchingIter worker -- keeps its own)."""
     import threading
-    if threading.current_thread() is threading.main_thread() or os.environ.get('SNIPER_PREFETCH_STREAM', '1') == '0':
+    if threading.current_thread() is threading.main_thread():
         return None
     try:
         import torch

@@ -87,8 +87,7 @@ class PrefetchingIter(mx.io.DataIter):
             # the worker's OWN stream: batch assembly is small uploads from pageable memory (synchronous copies: each waits for
             # everything queued before it on its stream) and small kernels -- on the consumer's stream every one of them would wait
             # for the training step in flight, and a batch took longer to assemble than a step to run (profiles/r05_fit_path.txt)
-            import os
-            if self.own_stream and os.environ.get('SNIPER_PREFETCH_STREAM', '1') != '0':      # (=0: never, A/B)
+            if self.own_stream:
                 stream = self._stream = torch.cuda.Stream(device=self._device)
                 torch.cuda.set_stream(stream)
         while True:

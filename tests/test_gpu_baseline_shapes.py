@@ -77,7 +77,7 @@ def test_deformable_psroi_pooling_at_6000_rois(with_trans):
     hip.call('sn_dpsroi_pool_fwd', dd, td(rois), None if trans is None else td(trans), out, R, H, W, C, P, S, 1.0 / SC, tstd, hip.stream())
     want = onn.dpsroi_pool_fast(f16r(data), rois, trans, P, S, 1.0 / SC, tstd)
     assert_close(out.float().cpu().numpy().transpose(0, 3, 1, 2), want, 1e-2, 1e-2, 'dpsroi fwd R=6000')
-    # the slab-stationary launch (what the executor calls: B known) writes the same rows, bit for bit; unsorted RoIs too
+    # the entry point with the image count B (what the executor calls) writes the same rows as the plain one, bit for bit; unsorted RoIs too
     out_s = torch.full((R, P, P, C), 7.0, dtype=torch.float16, device=dev())
     hip.call('sn_dpsroi_pool_fwd_images', dd, td(rois), None if trans is None else td(trans), out_s, R, B, H, W, C, P, S, 1.0 / SC, tstd,
              hip.stream())

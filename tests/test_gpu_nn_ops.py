@@ -343,11 +343,10 @@ def test_batchnorm_train_fwd_bwd():
 
 @pytest.mark.parametrize('M,C,nblk,relu', [(20480, 256, 128, 1), (20480, 1024, 128, 1), (2048, 64, 13, 0), (5000, 192, 160, 2),
                                            (20480, 256, 512, 1), (3000, 72, 19, 1)])
-def test_bn_finalize_fused_into_apply_and_dx_equals_the_separate_launches(M, C, nblk, relu):
-    """sn_bn_apply_blocks / sn_bn_backward_blocks (round 6: the finalize launch folded into the consumer, which re-reduces the
-    partials of its own 64-channel slab in the separate kernel's summation order) against the separate launches
-    (the default; the fused form is opt-in, sn_debug_option bn_fused_finalize: in the step it measured slower): every output BIT-equal -- y, scale, shift, saved statistics, moving averages; dx, dgamma,
-    dbeta (accumulated onto a non-zero arena).  nblk = 512 and C = 72 are shapes that keep the separate launches either way."""
+def test_bn_apply_and_backward_blocks_equal_the_separate_launches(M, C, nblk, relu):
+    """sn_bn_apply_blocks against sn_bn_finalize_blocks + sn_bn_apply on the same partials: scale, shift, saved statistics, moving
+    averages and y BIT-equal.  sn_bn_backward_blocks: dgamma / dbeta accumulated onto a non-zero arena, bit-equal to the dx = NULL
+    call (parameter gradients only) plus the arena; dx against the formula in float64."""
     hip = _hip()
     rs = np.random.RandomState(M + C + nblk)
     td = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(dev()).to(dt)
@@ -361,30 +360,46 @@ def test_bn_finalize_fused_into_apply_and_dx_equals_the_separate_launches(M, C, 
     bpart = td(rs.standard_normal((nblk, 2, C)) * 3)
     gamma, beta = td(rs.uniform(0.5, 1.5, C)), td(rs.standard_normal(C) * 0.1)
     ws = torch.empty(hip.query('sn_bn_workspace_bytes', M, C), dtype=torch.uint8, device=dev())
+    f = lambda v=0.0: torch.full((C,), v, dtype=torch.float32, device=dev())
     res = []
-    for fused in (0, 1):
-        hip.call('sn_debug_option', b'bn_fused_finalize', fused)
-        try:
-            f = lambda v=0.0: torch.full((C,), v, dtype=torch.float32, device=dev())
-            sc, sh, sm, si, rm, rv = f(7), f(7), f(7), f(7), f(0.25), f(1.5)
-            y = torch.full((M, C), 7.0, dtype=torch.float16, device=dev())
+    for blocks in (0, 1):
+        sc, sh, sm, si, rm, rv = f(7), f(7), f(7), f(7), f(0.25), f(1.5)
+        y = torch.full((M, C), 7.0, dtype=torch.float16, device=dev())
+        if blocks:
             hip.call('sn_bn_apply_blocks', part, nblk, x, y, M, C, C, C, 2e-5, 0.9, gamma, beta, rm, rv, sc, sh, sm, si, relu, hip.stream())
-            dx = torch.full((M, C), 7.0, dtype=torch.float16, device=dev())
-            dg, db = f(0.5), f(-0.5)
-            hip.call('sn_bn_backward_blocks', bpart, nblk, dy, x, acc, dx, M, C, C, C, C, C, sc, sh, sm, si, relu, ws, dg, db, hip.stream())
-            dg2, db2 = f(0.0), f(0.0)          # parameter gradients only (dx = NULL: a BatchNorm on a tensor that needs no gradient)
-            hip.call('sn_bn_backward_blocks', bpart, nblk, dy, x, None, None, M, C, C, C, C, C, sc, sh, sm, si, relu, ws, dg2, db2, hip.stream())
-            torch.cuda.synchronize()
-            res.append([t.clone() for t in (y, sc, sh, sm, si, rm, rv, dx, dg, db, dg2, db2)])
-        finally:
-            hip.call('sn_debug_option', b'bn_fused_finalize', 0)
-    names = 'y scale shift save_mean save_invstd run_mean run_var dx dgamma dbeta dgamma_only dbeta_only'.split()
-    for n, a, b in zip(names, res[0], res[1]):
+        else:
+            hip.call('sn_bn_finalize_blocks', part, nblk, M, C, 2e-5, 0.9, gamma, beta, rm, rv, sc, sh, sm, si, hip.stream())
+            hip.call('sn_bn_apply', x, y, M, C, C, C, sc, sh, relu, hip.stream())
+        res.append((y, sc, sh, sm, si, rm, rv))
+    for n, a, b in zip('y scale shift save_mean save_invstd run_mean run_var'.split(), res[0], res[1]):
         assert torch.equal(a, b), (n, float((a.float() - b.float()).abs().max()))
+    y, sc, sh, sm, si = res[1][:5]
+    dx = torch.full((M, C), 7.0, dtype=torch.float16, device=dev())
+    dg, db = f(0.5), f(-0.5)
+    hip.call('sn_bn_backward_blocks', bpart, nblk, dy, x, acc, dx, M, C, C, C, C, C, sc, sh, sm, si, relu, ws, dg, db, hip.stream())
+    dg2, db2 = f(0.0), f(0.0)          # parameter gradients only (dx = NULL: a BatchNorm on a tensor that needs no gradient)
+    hip.call('sn_bn_backward_blocks', bpart, nblk, dy, x, None, None, M, C, C, C, C, C, sc, sh, sm, si, relu, ws, dg2, db2, hip.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(dg, dg2 + 0.5) and torch.equal(db, db2 - 0.5)
+    # dx = scale * (g - dbeta / M - xhat * dgamma / M) + acc, g = dy masked by the activation of y (elements within 1e-3 of a
+    # mask edge left out: the kernel decides them on its own fp32 rounding of x * scale + shift)
+    d = lambda t: t.double()
+    yf = d(x) * d(sc) + d(sh)
+    keep, g = torch.ones_like(yf, dtype=torch.bool), d(dy)
+    if relu:
+        keep = (yf.abs() > 1e-3) & ((yf - 6).abs() > 1e-3)
+        ok = (yf > 0) & (yf <= 6) if relu == 2 else yf > 0
+        g = g * ok
+    sg, sgx = d(bpart[:, 0]).sum(0), d(bpart[:, 1]).sum(0)
+    assert_close(db2.cpu().numpy(), sg.cpu().numpy(), 1e-5, 1e-4, 'dbeta')
+    assert_close(dg2.cpu().numpy(), (sgx * d(si)).cpu().numpy(), 1e-5, 1e-4, 'dgamma')
+    want = d(sc) * (g - sg / M - (d(x) - d(sm)) * d(si) * (sgx * d(si)) / M) + d(acc)
+    got = d(dx)
+    assert_close(got[keep].cpu().numpy(), want[keep].cpu().numpy(), 1e-2, 1e-2 * float(want.abs().max()), 'dx')
     # and the statistics are right: mean / variance of the rows
     mean, var = xf.double().mean(0), xf.double().var(0, unbiased=False)
-    assert_close(res[1][3].cpu().numpy(), mean.cpu().numpy(), 1e-4, 1e-4, 'saved mean')
-    assert_close(res[1][4].cpu().numpy(), (1.0 / torch.sqrt(var + 2e-5)).cpu().numpy(), 1e-4, 1e-4, 'saved invstd')
+    assert_close(sm.cpu().numpy(), mean.cpu().numpy(), 1e-4, 1e-4, 'saved mean')
+    assert_close(si.cpu().numpy(), (1.0 / torch.sqrt(var + 2e-5)).cpu().numpy(), 1e-4, 1e-4, 'saved invstd')
 
 
 def test_bn_global_maxpool_ew_layout_ops():
@@ -979,7 +994,7 @@ def test_dpsroi_pool_fwd_bwd_vs_oracle(B, C, H, W, R, SC):
         hip.call('sn_dpsroi_pool_fwd', dd, td(rois), None if tr is None else td(tr), out, R, H, W, C, P, S, 1.0 / SC, tstd, hip.stream())
         want = onn.dpsroi_pool(f16r(data).astype(np.float64), rois, tr, P, S, 1.0 / SC, tstd)
         assert_close(out.float().cpu().numpy().transpose(0, 3, 1, 2), want, 1e-2, 1e-2, 'dpsroi fwd')
-        # the (image, 64-channel slab)-stationary kernel (taken with B known, C % 64 == 0, R >= 8 B): the per-RoI kernel's outputs
+        # the entry point with the image count B (what the executor calls) writes the same rows as the plain one, bit for bit
         out_s = torch.full((R, P, P, C), 7.0, dtype=torch.float16, device=dev())
         hip.call('sn_dpsroi_pool_fwd_images', dd, td(rois), None if tr is None else td(tr), out_s, R, B, H, W, C, P, S, 1.0 / SC, tstd,
                  hip.stream())

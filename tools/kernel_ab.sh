@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel A/B from rocprofv3 kernel statistics of the SAME short bench run under different environment overrides:
-#   tools/kernel_ab.sh "dpsroi|nms_lazy|topk|anchor_finish|copy" "" "SNIPER_DPSROI_NO_STAGE=1"
+#   tools/kernel_ab.sh "conv_dma|conv_igemm" "" "SNIPER_CONV_NO_PERSIST=1"
 # prints, per variant, calls / average us of the kernels whose name matches the pattern.
 PAT="$1"; shift
 ROOT=$(pwd)
