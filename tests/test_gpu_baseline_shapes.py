@@ -325,3 +325,30 @@ def test_conv_dgrad_bn_at_c2_launch_shapes_vs_oracle(name, act):
     assert_close(db.cpu().numpy(), want_dbeta, 1e-2, 1e-2 * np.abs(want_dbeta).max(), 'dbeta %s' % name)
     assert_close(dg.cpu().numpy(), want_dgamma, 1e-2, 1e-2 * np.abs(want_dgamma).max(), 'dgamma %s' % name)
     assert_close(from_nhwc(out), want_dbn, 1e-2, 1e-2 * np.abs(want_dbn).max(), 'BatchNorm input gradient %s' % name)
+
+
+@pytest.mark.parametrize('zero', [False, True])
+def test_deformable_sampling_at_c2_launch_shape(zero):
+    """The res5 deformable sampling at its C2 launch shape (20 chips, 512 channels, 32 x 32, 4 deformable groups, 3x3 / pad 2 /
+    dilation 2) as the graph launches it: fp16 offsets (about 1.5 sigma, or all zero as a fresh DCN starts), fp16 d_offset and
+    d_data, the max-|offset| workspace.  Images 0, 7 and 19 against the per-image float64 oracle."""
+    from sniper_amd import hip
+    from test_gpu_nn_ops import DCN_DIL, DCN_PAD, DCN_T, _dcn_run
+    N, C, H, W, DG = B, 512, 32, 32, 4
+    rs = np.random.RandomState(5 + zero)
+    data = rs.standard_normal((N, C, H, W)).astype(np.float32)
+    off = np.zeros((N, 2 * DCN_T * DG, H, W), np.float32) if zero else f16r(rs.standard_normal((N, 2 * DCN_T * DG, H, W)) * 1.5)
+    dcol = rs.standard_normal((N, H, W, DCN_T, C)).astype(np.float32)
+    dd = torch.from_numpy(np.ascontiguousarray(data.transpose(0, 2, 3, 1))).to(dev()).half()
+    offd = torch.from_numpy(np.ascontiguousarray(off.transpose(0, 2, 3, 1))).to(dev()).half()
+    col, d_data, d_off, wsd = _dcn_run(hip, dd, offd, torch.from_numpy(dcol).to(dev()).half(), N, H, W, C, DG, 1)
+    assert wsd[:4].view(torch.float32).item() == float(np.abs(off).max())
+    col = col.view(N, H, W, DCN_T, C)
+    for n in (0, 7, 19):
+        d64, o64 = f16r(data[n:n + 1]).astype(np.float64), off[n:n + 1].astype(np.float64)
+        want = onn.deform_im2col(d64, o64, 3, 3, 1, DCN_PAD, DCN_DIL, DG)
+        assert_close(col[n:n + 1].float().cpu().numpy(), want, 1e-2, 1e-2 * np.abs(want).max(), 'im2col image %d' % n)
+        del want
+        wd, wo = onn.deform_col2im(f16r(dcol[n:n + 1]).astype(np.float64), d64, o64, 3, 3, 1, DCN_PAD, DCN_DIL, DG)
+        assert_close(d_data[n:n + 1].float().cpu().numpy().transpose(0, 3, 1, 2), wd, 1e-2, 1e-2 * np.abs(wd).max(), 'd_data image %d' % n)
+        assert_close(d_off[n:n + 1].float().cpu().numpy().transpose(0, 3, 1, 2), wo, 1e-2, 1e-2 * np.abs(wo).max(), 'd_offset image %d' % n)

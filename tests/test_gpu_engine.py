@@ -829,3 +829,75 @@ def test_no_kernel_reads_uninitialised_memory(monkeypatch):
     assert max(rel(u, v) for u, v in zip(o0, o1)) <= 1e-6
     worst = max((rel(g0[n], g1[n]), n) for n in g0)
     assert worst[0] <= 1e-5, worst
+
+
+def _dcn_symbol(mx, head):
+    """one res5 deformable convolution spelled as resnet_mx_101_e2e.py spells it; training: MakeLoss(y * head) -> dy = head"""
+    data, offset = mx.sym.Variable('data'), mx.sym.Variable('offset')
+    y = mx.contrib.sym.DeformableConvolution(data=data, offset=offset, name='res5a_conv2', num_filter=512, kernel=(3, 3),
+                                             stride=(1, 1), pad=(2, 2), dilate=(2, 2), num_deformable_group=4, no_bias=True)
+    return mx.sym.MakeLoss(data=y * mx.sym.Variable('head'), name='loss') if head else y
+
+
+@pytest.mark.parametrize('N,H,W', [(2, 32, 32), (1, 13, 11)])
+def test_deformable_convolution_lowered_vs_float64(N, H, W):
+    """DeformableConvolutionStep as a whole -- sn_deform_im2col, the 1x1 GEMM over the (tap, channel) column, sn_conv_dgrad with
+    wT_flat, sn_deform_col2im with the max-|offset| workspace -- against a float64 restatement: oracle deform_im2col, the matmul,
+    oracle deform_col2im of the column gradient.  Bound for training (output; data, offset and weight gradients) and for inference
+    (output; the split-K column GEMM).  13 x 11: a pixel count that is not a multiple of 64."""
+    import sniper_amd.mx as mx
+    from oracle import nn as onn
+    from sniper_amd.engine.executor import Executor
+    C, O, DG, T = 512, 512, 4, 9
+    rs = np.random.RandomState(N * H + W)
+    x = rs.standard_normal((N, C, H, W)).astype(np.float32)
+    off = f16r(rs.standard_normal((N, 2 * T * DG, H, W)) * 1.5)
+    off[:, ::5] = np.rint(off[:, ::5])                          # some samples exactly on cells
+    w = (rs.standard_normal((O, C, 3, 3)) / np.sqrt(C * T)).astype(np.float32)
+    head = rs.standard_normal((N, O, H, W)).astype(np.float32)
+    x64, off64, w64, dy = f16r(x).astype(np.float64), off.astype(np.float64), f16r(w).astype(np.float64), f16r(head).astype(np.float64)
+    col = onn.deform_im2col(x64, off64, 3, 3, 1, 2, 2, DG).reshape(N * H * W, T * C)
+    wmat = w64.transpose(0, 2, 3, 1).reshape(O, T * C)                          # [o][(tap, c)]
+    want_y = (col @ wmat.T).reshape(N, H, W, O).transpose(0, 3, 1, 2)
+    dy_m = dy.transpose(0, 2, 3, 1).reshape(N * H * W, O)
+    want_dw = (dy_m.T @ col).reshape(O, 3, 3, C).transpose(0, 3, 1, 2)
+    want_dx, want_doff = onn.deform_col2im((dy_m @ wmat).reshape(N, H, W, T, C), x64, off64, 3, 3, 1, 2, 2, DG)
+    del col
+
+    shapes = dict(data=(N, C, H, W), offset=(N, 2 * T * DG, H, W), head=(N, O, H, W))
+    sym = _dcn_symbol(mx, True)
+    ex = Executor(sym, shapes, True)
+    ex.set_params({'res5a_conv2_weight': w}, {})
+    for node in ex.nodes:                      # the data and the offset field are produced by layers that need their gradients
+        if node.op is None and node.name in ('data', 'offset'):
+            ex.vals[(id(node), 0)].needs_grad = True
+    step = [s for s in ex.steps if type(s).__name__ == 'DeformableConvolutionStep'][0]
+    got, add_grad = {}, ex.add_grad
+
+    def spy(v, g, fmt):
+        if v.name in ('data', 'offset'):
+            got[v.name] = (g.clone(), fmt)
+        return add_grad(v, g, fmt)
+    ex.add_grad = spy
+    ex.forward(dict(data=x, offset=off, head=head), is_train=True)
+    y = step.y.t.clone()
+    ex.backward()
+    torch.cuda.synchronize()
+    assert_close(y.float().cpu().numpy().transpose(0, 3, 1, 2), want_y, 1e-2, 1e-2 * np.abs(want_y).max(), 'dcn train output')
+    assert got['data'][1] == 'act' and got['offset'][1] == 'act'
+    dx = got['data'][0].float().cpu().numpy().transpose(0, 3, 1, 2)
+    doff = got['offset'][0].float().cpu().numpy().transpose(0, 3, 1, 2)
+    assert_close(dx, want_dx, 1e-2, 1e-2 * np.abs(want_dx).max(), 'dcn d_data')
+    assert_close(doff, want_doff, 1e-2, 1e-2 * np.abs(want_doff).max(), 'dcn d_offset')
+    p = ex.params['res5a_conv2_weight']
+    dw = p.to_reference(p.grad.detach().cpu().numpy())
+    # (fp32 output, but a contraction of the fp16 column and fp16 dy over N*H*W pixels: the wgrad tests' 1e-2)
+    assert_close(dw, want_dw, 1e-2, 1e-2 * np.abs(want_dw).max(), 'dcn d_weight')
+
+    ex_i = Executor(_dcn_symbol(mx, False), dict(data=shapes['data'], offset=shapes['offset']), False)
+    ex_i.set_params({'res5a_conv2_weight': w}, {})
+    out = ex_i.forward(dict(data=x, offset=off), is_train=False)[0]
+    torch.cuda.synchronize()
+    step_i = [s for s in ex_i.steps if type(s).__name__ == 'DeformableConvolutionStep'][0]
+    assert step_i._splitk_bytes > 0                 # the test-time split-K launch ran
+    assert_close(out.cpu().numpy(), want_y, 1e-2, 1e-2 * np.abs(want_y).max(), 'dcn inference output')

@@ -1243,3 +1243,276 @@ def test_stem_conv_3x3_wgrad_packed():
     want = wt.grad.numpy().transpose(0, 2, 3, 1)
     assert_close(got[:, :, :K, :3], want, 1e-2, 1e-2 * np.abs(want).max(), 'stem wgrad')
     assert float(np.abs(got[:, :, :, 3]).max()) == 0.0            # channel padding carries no gradient
+
+
+# ---------------------------------------------------------------------------------------------
+# Deformable sampling as DeformableConvolutionStep launches it (engine/ops.py): fp16 offsets (offset_dtype 0: the half_t
+# instantiations of the im2col, offset-gradient, absmax and data-gradient kernels), fp16 d_offset, fp16 d_data, the max-|offset|
+# workspace that prunes the data gradient's candidate scan.  3x3, pad 2, dilation 2 (resnet_mx_101_e2e.py:73-76).
+# ---------------------------------------------------------------------------------------------
+DCN_PAD, DCN_DIL, DCN_T = 2, 2, 9
+DCN_DMAX_FRAC = 4.0 - 2.0 ** -9      # 3.998046875: the largest fp16 value below 4 -> ceil(D) = 4, floor(D) = 3
+
+
+def _dcn_offsets(rs, N, DG, H, W, dmax):
+    """Offsets (N, 2*T*DG, H, W), every value exact in fp16 and |offset| <= dmax = the launch maximum.  A random field of about
+    1.5 sigma with samples placed on the edges of the sampling rule: exact zeros, integers (on a cell: the one-sided offset
+    gradient), exactly on row / column H-1 / W-1 (the clamped border branch), exactly on 0 and at -1/1024 (just outside: nothing),
+    exactly on H / W (just outside at the far border: nothing), on the far edge of a 4 x 4 data tile (a footprint in two tiles),
+    |offset| = dmax, beyond the image.  Then, per image and group, the four samples at the edges of the pruned scan's window
+    (deform_col2im_data_mfma_kernel: oy_lo .. oy_hi, ox_lo .. ox_hi from Di = ceil(D) + 1): |offset| = dmax towards a tile whose
+    rows / columns the sample just reaches (with dmax = k + 0.998: a window of floor(D) drops them)."""
+    T, C2 = DCN_T, 2 * DCN_T * DG
+    off = f16r(np.clip(rs.standard_normal((N, C2, H, W)) * 1.5, -dmax, dmax)).astype(np.float64)
+    ch = np.arange(C2)
+    tap, comp = ch // 2 % T, ch % 2                                  # comp 0: y, 1: x
+    k = np.where(comp == 0, tap // 3, tap % 3)[None, :, None, None]
+    o = np.where(comp[None, :, None, None] == 0, np.arange(H)[None, None, :, None], np.arange(W)[None, None, None, :])
+    base = np.broadcast_to(o - DCN_PAD + k * DCN_DIL, off.shape).astype(np.float64)      # sampling position at offset 0
+    dim = np.broadcast_to(np.where(comp == 0, H, W)[None, :, None, None], off.shape).astype(np.float64)
+    frac = rs.choice([0.25, 0.5, 0.75, 1.0 - 2.0 ** -9], size=off.shape)
+    cands = [np.zeros(off.shape), np.rint(rs.uniform(-dmax, dmax, off.shape)), dim - 1 - base, -base, -base - 1.0 / 1024,
+             dim - base, np.floor(base / 4) * 4 + 3 + frac - base, np.floor(base / 4) * 4 - 1 + frac - base,
+             rs.choice([-dmax, dmax], size=off.shape), dim + 1 - base, -2 - base]
+    cat = rs.randint(0, len(cands) + 3, size=off.shape)             # (the last three: keep the random value)
+    for i, c in enumerate(cands):
+        ok = (cat == i) & (np.abs(c) <= dmax) & (f16r(c) == c)
+        off[ok] = c[ok]
+    kk = int(np.ceil(dmax)) - 1           # dmax = kk + 0.998 (or kk + 1)
+    for n in range(N):
+        for g in range(DG):
+            b = g * 2 * T
+            # y: tile row 8 reached from above by tap kh = 2 (py = 8 - 0.002), tile row 4..7 from below by tap kh = 0 (py = 7.002)
+            off[n, b + 2 * 7, 8 - kk - 3, W // 2] = dmax
+            off[n, b + 2 * 7 + 1, 8 - kk - 3, W // 2] = 0.0
+            off[n, b + 2 * 1, 4 + kk + 6, W // 2 - 1] = -dmax
+            off[n, b + 2 * 1 + 1, 4 + kk + 6, W // 2 - 1] = 0.0
+            # x: the same with taps kw = 2 / kw = 0
+            off[n, b + 2 * 5 + 1, H // 2, 8 - kk - 3] = dmax
+            off[n, b + 2 * 5, H // 2, 8 - kk - 3] = 0.0
+            off[n, b + 2 * 3 + 1, H // 2 - 1, 4 + kk + 6] = -dmax
+            off[n, b + 2 * 3, H // 2 - 1, 4 + kk + 6] = 0.0
+    assert np.array_equal(f16r(off), off) and float(np.abs(off).max()) == dmax
+    return off.astype(np.float32)
+
+
+def _dcn_run(hip, dd, offd, dcd, N, H, W, C, DG, prune):
+    """im2col + col2im with fp16 offsets (the production launch); outputs filled with 7.0 first.  -> col, d_data, d_offset, ws"""
+    T, oc = DCN_T, 2 * DCN_T * DG
+    col = torch.full((N * H * W, T, C), 7.0, dtype=torch.float16, device=dev())
+    hip.call('sn_deform_im2col', dd, offd, col, N, H, W, C, 3, 3, 1, DCN_PAD, DCN_DIL, DG, oc, 0, hip.stream())
+    d_data = torch.full((N, H, W, C), 7.0, dtype=torch.float16, device=dev())
+    d_off = torch.full((N, H, W, oc), 7.0, dtype=torch.float16, device=dev())
+    wsd = torch.full((16,), 0x55, dtype=torch.uint8, device=dev()) if prune else None
+    hip.call('sn_deform_col2im', dcd, dd, offd, d_data, 0, d_off, N, H, W, C, 3, 3, 1, DCN_PAD, DCN_DIL, DG, oc, 0, wsd, hip.stream())
+    torch.cuda.synchronize()
+    return col, d_data, d_off, wsd
+
+
+@pytest.mark.parametrize('C,DG', [(512, 4), (64, 1), (512, 1), (32, 4)])
+def test_deformable_sampling_fp16_offsets_vs_oracle(C, DG):
+    """The fp16-offset kernels against oracle/nn.py at engineered offsets (_dcn_offsets), pruned and unpruned data gradient.
+    (512, 4): the production groups (cg = 128); (512, 1): cg = 512, two 256-channel slabs of the data-gradient kernel; (32, 4):
+    cg = 8, one lane per group in the offset gradient's reduction.  Launch maxima k + 0.998 (the window's ceil), an integer, and
+    all-zero offsets (a fresh DCN: every sample on a cell, the smallest window Di = 1)."""
+    hip = _hip()
+    N, H, W = 2, 16, 18
+    rs = np.random.RandomState(C + DG)
+    data = rs.standard_normal((N, C, H, W)).astype(np.float32)
+    dcol = rs.standard_normal((N, H, W, DCN_T, C)).astype(np.float32)
+    dd, dcd = to_nhwc_f16(data), torch.from_numpy(dcol).to(dev()).half()
+    data64, dcol64 = f16r(data).astype(np.float64), f16r(dcol).astype(np.float64)
+    for dmax in (DCN_DMAX_FRAC, 4.0, 0.0):
+        off = _dcn_offsets(rs, N, DG, H, W, dmax) if dmax else np.zeros((N, 2 * DCN_T * DG, H, W), np.float32)
+        offd = torch.from_numpy(np.ascontiguousarray(off.transpose(0, 2, 3, 1))).to(dev()).half()
+        want_col = onn.deform_im2col(data64, off.astype(np.float64), 3, 3, 1, DCN_PAD, DCN_DIL, DG)
+        want_dd, want_do = onn.deform_col2im(dcol64, data64, off.astype(np.float64), 3, 3, 1, DCN_PAD, DCN_DIL, DG)
+        runs = {}
+        for prune in (1, 0):
+            col, d_data, d_off, wsd = runs[prune] = _dcn_run(hip, dd, offd, dcd, N, H, W, C, DG, prune)
+            what = 'C=%d DG=%d max|offset|=%g prune=%d' % (C, DG, dmax, prune)
+            assert_close(col.float().cpu().numpy().reshape(want_col.shape), want_col, 1e-2, 1e-2 * np.abs(want_col).max(), 'im2col ' + what)
+            assert_close(from_nhwc(d_data), want_dd, 1e-2, 1e-2 * np.abs(want_dd).max(), 'd_data ' + what)
+            assert_close(d_off.float().cpu().numpy().transpose(0, 3, 1, 2), want_do, 1e-2, 1e-2 * np.abs(want_do).max(), 'd_offset ' + what)
+            if prune:
+                assert wsd[:4].view(torch.float32).item() == dmax
+        # the column and the offset gradient do not depend on the workspace (the data gradient of the pruned scan can differ from
+        # the full scan's by rounding: its entry list fills -- and is flushed to the matrix cores -- at other points)
+        assert torch.equal(runs[1][0], runs[0][0]) and torch.equal(runs[1][2], runs[0][2])
+
+
+def test_deformable_sampling_nan_offset():
+    """A NaN offset samples nothing: the outputs are bit-equal to a run with that offset at +1e4 (outside the image; the absmax is
+    then large enough to open the window completely, as +inf does), its two d_offset entries are 0, the absmax workspace is +inf."""
+    hip = _hip()
+    N, C, H, W, DG = 1, 128, 16, 16, 4
+    rs = np.random.RandomState(77)
+    dd = to_nhwc_f16(rs.standard_normal((N, C, H, W)).astype(np.float32))
+    dcd = torch.from_numpy(rs.standard_normal((N, H, W, DCN_T, C)).astype(np.float32)).to(dev()).half()
+    off = _dcn_offsets(rs, N, DG, H, W, DCN_DMAX_FRAC).transpose(0, 2, 3, 1).copy()
+    ch = 2 * (2 * DCN_T + 4)                # group 2, tap 4, y component
+    runs = []
+    for v in (np.nan, 1e4):
+        o = off.copy()
+        o[0, 5, 6, ch] = v
+        runs.append(_dcn_run(hip, dd, torch.from_numpy(o).to(dev()).half(), dcd, N, H, W, C, DG, 1))
+    nan_run, far_run = runs
+    for a, b in zip(nan_run[:3], far_run[:3]):
+        assert torch.equal(a, b)
+    assert float(nan_run[2][0, 5, 6, ch]) == 0.0 and float(nan_run[2][0, 5, 6, ch + 1]) == 0.0
+    assert torch.isfinite(nan_run[1]).all() and torch.isfinite(nan_run[2]).all()
+    assert nan_run[3][:4].view(torch.float32).item() == float('inf')
+    assert far_run[3][:4].view(torch.float32).item() == 1e4
+
+
+# ---------------------------------------------------------------------------------------------
+# BatchNorm statistics at a large mean-to-std ratio: the variance is E[y^2] - mean^2 of fp32 partial sums
+# ---------------------------------------------------------------------------------------------
+BN_EPS = 2e-5
+
+
+def _large_mean_channels(rs, C):
+    """per channel (mean, std): mean/std ratios 0, 10, 30, 100 and constant channels (std 0), std in {0.25, 1, 4}.  The fp16
+    spacing at the mean is at most 2^-10 of it: 0.1 std at a ratio of 100 (mean 400, spacing 0.25, std 4), 0.03 std at 30 --
+    the stored values keep a spread the float64 statistics below are taken of."""
+    kind = np.arange(C) % 5
+    std = rs.choice([0.25, 1.0, 4.0], size=C)
+    mean = np.array([0.0, 10.0, 30.0, 100.0, 0.0])[kind] * std * rs.choice([-1.0, 1.0], size=C)
+    const = kind == 4
+    mean[const] = rs.choice([37.5, -0.75, 1000.0, 0.0], size=int(const.sum()))
+    std[const] = 0.0
+    return mean, std, const
+
+
+def _check_bn_coefs(y, const, gamma, beta, rm0, rv0, got, what):
+    """got = (scale, shift, save_mean, save_invstd, run_mean, run_var) of a finalize over the statistics of y (M, C), the stored fp16
+    values, against float64 two-pass statistics of y.  invstd within 1e-3 relative; a constant channel (variance 0) gets
+    invstd = 1/sqrt(eps) exactly."""
+    sc, sh, sm, si, rm, rv = [t.double().cpu().numpy() for t in got]
+    mean = y.mean(0)
+    var = ((y - mean) ** 2).mean(0)
+    std = np.sqrt(var)
+    invstd = 1.0 / np.sqrt(var + np.float64(np.float32(BN_EPS)))
+    assert_close(sm, mean, 1e-6, 1e-3 * std + 1e-6, 'save_mean ' + what)
+    assert_close(si, invstd, 1e-3, 0, 'save_invstd ' + what)
+    assert np.all(si[const] == np.float32(1.0 / np.sqrt(np.float64(np.float32(BN_EPS))))), 'invstd of a constant channel ' + what
+    assert_close(sc, gamma * invstd, 1e-3, 0, 'scale ' + what)
+    assert_close(sh, beta - mean * gamma * invstd, 1e-5, 1e-3 * np.abs(mean * gamma * invstd) + 1e-5, 'shift ' + what)
+    assert_close(rm, 0.9 * rm0 + 0.1 * mean, 1e-5, 1e-4 * std + 1e-6, 'run_mean ' + what)
+    assert_close(rv, 0.9 * rv0 + 0.1 * var, 1e-5, 2e-4 * var + 1e-6, 'run_var ' + what)
+
+
+def _bn_finalize_and_apply(hip, y_d, M, C, part, nblk, seed, what):
+    """finalize (sn_bn_finalize on sn_bn_stats' workspace when nblk is None, else sn_bn_finalize_blocks) + sn_bn_apply, checked"""
+    rs = np.random.RandomState(seed)
+    gamma, beta = rs.uniform(0.5, 1.5, C), rs.standard_normal(C) * 0.1
+    rm0, rv0 = rs.standard_normal(C), rs.uniform(0.5, 2.0, C)
+    td = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(dev())
+    g_d, b_d, rm, rv = td(gamma), td(beta), td(rm0), td(rv0)
+    sc, sh, sm, si = [torch.full((C,), 7.0, device=dev()) for _ in range(4)]
+    if nblk is None:
+        hip.call('sn_bn_finalize', part, M, C, BN_EPS, 0.9, g_d, b_d, rm, rv, sc, sh, sm, si, hip.stream())
+    else:
+        hip.call('sn_bn_finalize_blocks', part, nblk, M, C, BN_EPS, 0.9, g_d, b_d, rm, rv, sc, sh, sm, si, hip.stream())
+    out = torch.full_like(y_d, 7.0)
+    hip.call('sn_bn_apply', y_d, out, M, C, C, C, sc, sh, 0, hip.stream())
+    torch.cuda.synchronize()
+    y = y_d.double().cpu().numpy().reshape(M, C)
+    const = y.std(0) == 0
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    _check_bn_coefs(y, const, f32(gamma), f32(beta), f32(rm0), f32(rv0), (sc, sh, sm, si, rm, rv), what)
+    want = (y - y.mean(0)) / np.sqrt(y.var(0) + np.float64(np.float32(BN_EPS))) * f32(gamma) + f32(beta)
+    assert_close(out.double().cpu().numpy().reshape(M, C), want, 1e-2, 1e-2 * np.abs(want).max(), 'applied ' + what)
+
+
+@pytest.mark.parametrize('M,C', [(3, 64), (200, 64), (20480, 256), (1024, 2048)])
+def test_bn_stats_large_mean_vs_two_pass(M, C):
+    """sn_bn_stats + sn_bn_finalize + sn_bn_apply with mean/std up to 100 and constant channels: M = 3, M = 200 (one row block of
+    C = 64: 256 rows), 20 480 rows in 320 row blocks, and 1024 rows of 2048 channels in 128 row blocks of 8 rows."""
+    hip = _hip()
+    rs = np.random.RandomState(M + C)
+    mean, std, const = _large_mean_channels(rs, C)
+    x = (mean + std * rs.standard_normal((M, C))).astype(np.float32)
+    if C == 2048:
+        # half of the constant channels take two fp16 levels 0.5 apart, below 724 in magnitude (mean/std about 2700): a partial
+        # over 8 rows of them is exact in fp32 ((2 x)^2 <= 2^21), so the float64 sum over the 128 blocks gives the variance
+        # exactly -- a float sum of the partials would not.  (At such a ratio the fp32 partials of longer row blocks do not.)
+        two = np.flatnonzero(const)[::2]
+        x[:, two] = rs.choice([600.5, -700.0, 650.0, -710.5], size=len(two)) + 0.5 * rs.randint(0, 2, size=(M, len(two)))
+    x_d = torch.from_numpy(x).to(dev()).half()
+    ws = torch.full((hip.query('sn_bn_workspace_bytes', M, C),), 0x55, dtype=torch.uint8, device=dev())
+    hip.call('sn_bn_stats', x_d, M, C, C, ws, hip.stream())
+    _bn_finalize_and_apply(hip, x_d, M, C, ws, None, M, 'sn_bn_stats M=%d C=%d' % (M, C))
+
+
+@pytest.mark.parametrize('N,H,C,O', [(3, 17, 64, 192), (4, 32, 64, 256)])
+def test_conv_stats_epilogue_large_mean_vs_two_pass(N, H, C, O):
+    """sn_conv_fwd_stats (a 1x1 convolution whose bias sets the mean) + sn_bn_finalize_blocks + sn_bn_apply, mean/std up to 100
+    and constant channels (zero weight rows: y = bias)."""
+    hip = _hip()
+    M = N * H * H
+    nblk = hip.query('sn_conv_fwd_stats_blocks', N, H, H, C, C, O, O, 0, 1, 1, 1, 0, 1)
+    assert nblk > 0
+    rs = np.random.RandomState(N * H + O)
+    mean, std, const = _large_mean_channels(rs, O)
+    x = rs.standard_normal((M, C)).astype(np.float32)
+    w = (rs.standard_normal((O, C)) * (std / np.sqrt(C))[:, None]).astype(np.float32)
+    x_d, w_d = torch.from_numpy(x).to(dev()).half(), torch.from_numpy(w).to(dev()).half()
+    b_d = torch.from_numpy(mean.astype(np.float32)).to(dev())
+    y = torch.full((M, O), 7.0, dtype=torch.float16, device=dev())
+    part = torch.full((nblk, 2, O), 7.0, dtype=torch.float32, device=dev())
+    hip.call('sn_conv_fwd_stats', x_d, w_d, b_d, None, y, N, H, H, C, C, O, O, 0, 1, 1, 1, 0, 1, 0, part, hip.stream())
+    _bn_finalize_and_apply(hip, y, M, O, part, nblk, M + O, 'conv stats N=%d H=%d O=%d' % (N, H, O))
+
+
+# ---------------------------------------------------------------------------------------------
+# small fp32 kernels of every step: sn_ew_f32 (gradient accumulation, hyper-parameter fill, scalar ops), the loss flags
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n', [1, 255, 257, 100003])
+def test_ew_f32_bit_equal_to_cpu(n):
+    """every op code (0 a-b, 1 a+b, 2 a*b, 3 a*scalar, 4 fill) on slices that start 4 / 12 / 8 bytes past a 16-byte boundary: the
+    same bits as the fp32 operation on the CPU, nothing written outside the slice"""
+    hip = _hip()
+    rs = np.random.RandomState(n)
+    a, b = (rs.standard_normal(n + 4) * 3).astype(np.float32), (rs.standard_normal(n + 4) * 3).astype(np.float32)
+    a_d, b_d = torch.from_numpy(a).to(dev()), torch.from_numpy(b).to(dev())
+    x, y, s = a[1:1 + n], b[3:3 + n], np.float32(-0.3711)
+    want = [x - y, x + y, x * y, x * s, np.full(n, s, np.float32)]
+    for op in range(5):
+        out = torch.full((n + 4,), 7.0, dtype=torch.float32, device=dev())
+        hip.call('sn_ew_f32', a_d[1:] if op < 4 else None, b_d[3:] if op < 3 else None, out[2:], n, op, float(s), hip.stream())
+        got = out.cpu().numpy()
+        assert np.array_equal(got[2:2 + n].view(np.int32), want[op].view(np.int32)), 'op %d n %d' % (op, n)
+        assert np.all(got[:2] == 7.0) and np.all(got[2 + n:] == 7.0), 'op %d n %d wrote outside its slice' % (op, n)
+
+
+@pytest.mark.parametrize('use_ignore,normalize_valid', [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_softmax_output_bwd_flag_combinations(use_ignore, normalize_valid):
+    """grad = grad_scale / (normalize_valid ? max(1, #valid) : 1) * (p - onehot(label)), 0 where use_ignore and label == ignore;
+    with use_ignore = 0 a label of -1 is valid and matches no class (gradient p).  RPN (B, 2, inner) and RCNN (R, 81) layouts,
+    grad_scale 1 / 0.37 / 3*100/64, and a batch whose labels are all -1."""
+    hip = _hip()
+    rs = np.random.RandomState(11 + 2 * use_ignore + normalize_valid)
+    for outer, K, inner in ((3, 2, 21 * 8 * 8), (300, 81, 1)):
+        x = rs.standard_normal((outer, K, inner)).astype(np.float32)
+        p = torch.softmax(torch.from_numpy(x), 1).numpy()
+        p_d = torch.from_numpy(p).to(dev())
+        ws = torch.full((4,), 12345, dtype=torch.int32, device=dev())
+        labs = (rs.choice([-1, 0, 1, K - 1], size=(outer, inner), p=[0.6, 0.2, 0.1, 0.1]).astype(np.float32),
+                np.full((outer, inner), -1.0, np.float32))
+        for lab in labs:
+            valid = (lab != -1) if use_ignore else np.ones(lab.shape, bool)
+            onehot = (lab[:, None, :] == np.arange(K)[None, :, None]).astype(np.float64)
+            for gs in (1.0, 0.37, 3 * 100.0 / 64.0):
+                g = torch.full_like(p_d, 7.0)
+                hip.call('sn_softmax_output_bwd', p_d, torch.from_numpy(lab).to(dev()), g, outer, K, inner, -1.0, use_ignore, gs,
+                         normalize_valid, ws, hip.stream())
+                mul = np.float64(np.float32(gs)) / (max(1, int(valid.sum())) if normalize_valid else 1)
+                want = mul * (p.astype(np.float64) - onehot) * valid[:, None, :]
+                got = g.cpu().numpy()
+                what = 'softmax bwd use_ignore=%d normalize_valid=%d grad_scale=%g (%d,%d,%d) %s' % (
+                    use_ignore, normalize_valid, gs, outer, K, inner, 'all -1' if (lab == -1).all() else '')
+                assert np.isfinite(got).all(), what
+                if not valid.any():
+                    assert np.all(got == 0.0), what
+                assert_close(got, want, 1e-5, 1e-6 * max(np.abs(want).max(), 1e-30), what)
