@@ -2,6 +2,11 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: DIR/<name>.npy)
+    python bench.py ... --full                             (also everything below "Extra objects")
+
+A plain run sets up, warms up, times the K steps and prints one JSON line: the metric and the fields that say how it was
+taken (config, device, graphs).  --full adds, after the timed steps, the measurements below; they run steps, passes and
+processes of their own and leave the headline figure alone.
 
 Workload (config.workload): BASELINE configs[1] -- ResNet-101 Faster-RCNN SNIPER, 3-scale chips,
 20 x 512 x 512 chips per GPU, fp16 storage / fp32 accumulate, seeded synthetic COCO-shaped data
@@ -14,7 +19,7 @@ minibatch (weak scaling, no sync-BN); value = N * B * K / max-over-ranks time.
 NOT inside the step: the epoch chip database (chip generation / box assignment, a1-a4 of SURVEY section 8) and image
 decoding / resizing -- they run once per epoch / ahead of the step and the chips are resident when the clock starts.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel family (implicit-GEMM MFMA convolution: forward + data gradient + weight gradient
                 launches) measured live with HIP events recorded on the stream each kernel is launched on, in extra untimed
                 steps run eagerly (the timed region replays hipGraphs, inside which nothing can be bracketed):
@@ -815,11 +820,13 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=20, help='chips per GPU (BASELINE C2: 20)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--inference', action='store_true', help='(default on rank 0 at N = 1; kept for old command lines)')
-    ap.add_argument('--no-inference', action='store_true', help='skip BASELINE config C5 (inf images/sec)')
-    ap.add_argument('--no-fit-path', action='store_true', help='skip the reference main_train.py throughput leg (fit_path)')
-    ap.add_argument('--no-c4', action='store_true', help='skip BASELINE config C4 (R-FCN head, 16 chips) at one GPU\'s share')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the conv roofline, the host cost of a '
+                    'step, the CPU baselines, BASELINE configs C4 and C5, fit_path and (N > 1) the all-reduce; print the full record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baselines')
+    ap.add_argument('--inference', action='store_true', help='(--full: default on rank 0 at N = 1; kept for old command lines)')
+    ap.add_argument('--no-inference', action='store_true', help='(--full) skip BASELINE config C5 (inf images/sec)')
+    ap.add_argument('--no-fit-path', action='store_true', help='(--full) skip the reference main_train.py throughput leg (fit_path)')
+    ap.add_argument('--no-c4', action='store_true', help='(--full) skip BASELINE config C4 (R-FCN head, 16 chips) at one GPU\'s share')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     if args.steps < 1:
@@ -882,10 +889,31 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * args.batch * args.steps / dt
-    dumped = None
+    ex = tr.mod.exe
+    head = {
+        'metric': 'train chips/sec (512x512, R101)', 'value': round(value, 2), 'unit': 'chips/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3), 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f16', 'data': 'synthetic',
+        'host_enqueue_ms_per_step': round(host_dt / args.steps * 1e3, 3), 'graphs': bool(ex.use_graphs and ex._graph_fb is not None),
+        'config': {'workload': 'ResNet-101 Faster-RCNN SNIPER 3-scale, batch %d x 512x512 fp16 per GPU (BASELINE configs[1]); '
+                               'step = GPU anchor labelling + fwd + bwd + grad all-reduce + SGD on HBM-resident chips (epoch chip generation / box '
+                               'assignment and image decode+resize are outside the step); f16 MFMA operands, f32 accumulation / losses / '
+                               'master weights' % args.batch,
+                   'chips_per_gpu': args.batch, 'global_batch': args.batch * world, 'parallelism': 'dp%d' % world},
+        'device': dict(device, sampled='sysfs levels read after the timed steps were enqueued, before the closing synchronise '
+                                       '(the device is still executing them)'),
+    }
     if args.dump_outputs and rank == 0:
         # before any further step: the network outputs are the executor's buffers, which the next step overwrites
-        dumped = dump_outputs(args.dump_outputs, last[0], last[1], tr.mod.output_names, tr.mod.get_params()[0])
+        head['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dump_outputs(args.dump_outputs, last[0], last[1],
+                                                                                 tr.mod.output_names, tr.mod.get_params()[0])}
+    if not args.full:
+        # a plain run ends here: everything below runs steps, passes or processes of its own
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- host cost of one step with an idle device: enqueue only, nothing waited for (host_dt above is throttled by the
     # launch queue once the host runs ahead of the device, so it is an upper bound, not the host's own time)
@@ -894,8 +922,6 @@ def main():
     step(0)
     host_idle_ms = (time.perf_counter() - t1) * 1e3
     sync()
-    ex = tr.mod.exe
-    graphs_used = bool(ex.use_graphs and ex._graph_fb is not None)
 
     # ---- roofline of the dominant kernel family, live HIP-event timing (untimed extra steps)
     # The timed region replays hipGraphs; for per-launch HIP events the same step is run eagerly (same kernels, same
@@ -1004,24 +1030,9 @@ def main():
         except Exception as e:   # noqa: BLE001 -- a report
             c4 = {'value': None, 'sample': 'failed: %r' % (e,)}
     if rank == 0:
-        out = {
-            'metric': 'train chips/sec (512x512, R101)', 'value': round(value, 2), 'unit': 'chips/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f16', 'data': 'synthetic',
-            'host_enqueue_ms_per_step': round(host_dt / args.steps * 1e3, 3), 'host_enqueue_idle_device_ms': round(host_idle_ms, 3),
-            'graphs': graphs_used, 'rpn_heads_dtype': 'f16 MFMA operands, f32 accumulate (reference: f32 after its Cast, resnet_mx_101_e2e.py:250-252)',
-            'config': {'workload': 'ResNet-101 Faster-RCNN SNIPER 3-scale, batch %d x 512x512 fp16 per GPU (BASELINE configs[1]); '
-                                   'step = GPU anchor labelling + fwd + bwd + grad all-reduce + SGD on HBM-resident chips (epoch chip generation / box '
-                                   'assignment and image decode+resize are outside the step); f16 MFMA operands, f32 accumulation / losses / '
-                                   'master weights' % args.batch,
-                       'chips_per_gpu': args.batch, 'global_batch': args.batch * world, 'parallelism': 'dp%d' % world},
-            'device': dict(device, sampled='sysfs levels read after the timed steps were enqueued, before the closing synchronise '
-                                           '(the device is still executing them)'),
-            'library_sources_hash': library_sources_hash(),
-            'roofline': roof, 'cpu_baseline': cpu,
-        }
-        if dumped is not None:
-            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
+        out = dict(head, host_enqueue_idle_device_ms=round(host_idle_ms, 3),
+                   rpn_heads_dtype='f16 MFMA operands, f32 accumulate (reference: f32 after its Cast, resnet_mx_101_e2e.py:250-252)',
+                   library_sources_hash=library_sources_hash(), roofline=roof, cpu_baseline=cpu)
         if dist_report is not None:
             out['dist'] = dist_report
         if fit_path is not None:

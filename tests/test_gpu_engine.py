@@ -703,7 +703,7 @@ def test_r101_c4_rfcn_head_parity_vs_cpu_reference_ops(B):
 
 
 def test_bench_two_rank_control_flow():
-    """`bench.py --gpus 2` launched the way the driver does (torch.distributed.run, one process per rank), rehearsed on ONE
+    """`bench.py --gpus 2 --full` launched the way the driver does (torch.distributed.run, one process per rank), rehearsed on ONE
     GPU: both ranks share the device and the gradient all-reduce goes through gloo (SNIPER_DIST_BACKEND) -- not a
     measurement, a guard for the collective call pattern: every rank must enter every all-reduce (a rank-0-only profiling
     step once deadlocked here), and rank 0 alone prints the JSON line."""
@@ -714,7 +714,8 @@ def test_bench_two_rank_control_flow():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SNIPER_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', '29531', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '2', '--batch', '4']
+           '--master-port', '29531', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '2', '--batch', '4',
+           '--full']
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -727,6 +728,28 @@ def test_bench_two_rank_control_flow():
     assert ds['rccl_ranks_seen'] == 2 and ds['backend'] == 'gloo' and ds['allreduce_ms'] > 0 and ds['allreduce_mb'] > 100
     assert ds['split_backward'] is True and 0.0 <= ds['overlap_frac'] <= 1.0 and ds['first_segment_ms'] > 0
     assert len(lines[0]) < 4096
+
+
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """`bench.py` without --full: the timed steps, the --dump-outputs arrays and ONE JSON line with the metric and how it was
+    taken -- none of the --full legs, which run steps, passes and processes of their own."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4',
+           '--dump-outputs', str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1 and 'BENCH_DETAIL' not in r.stdout, r.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d['metric'] == 'train chips/sec (512x512, R101)' and d['unit'] == 'chips/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f16' and d['steps'] == 2 and d['warmup'] == 1 and d['config']['chips_per_gpu'] == 4
+    assert abs(d['value'] * d['ms_per_step'] / 4000.0 - 1.0) < 1e-3          # value = chips / timed seconds
+    assert not set(d) & {'roofline', 'cpu_baseline', 'inference', 'fit_path', 'c4', 'dist', 'host_enqueue_idle_device_ms'}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + '.npy' for n in d['dump_outputs']['arrays'])
 
 
 def test_training_is_bitwise_reproducible():
