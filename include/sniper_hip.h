@@ -335,6 +335,18 @@ int sn_bn_backward(const void *dy, const void *x, const void *accumulate, void *
 int sn_bn_backward_blocks(const float *partials, int nblk, const void *dy, const void *x, const void *accumulate, void *dx, int M,
                           int C, int ps_dy, int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean,
                           const float *invstd, int relu, void *ws, float *dgamma, float *dbeta, sn_stream_t stream);
+/* Moving-statistics BatchNorm (use_global_stats=True) inside a TRAINING graph (fix_bn): y = act(x*scale + shift) with constant
+ * statistics, so dx = scale * g [+ accumulate] (g = dy where the activation passes), dbeta += sum g,
+ * dgamma += sum g * (x - mean) / sqrt(var + eps).  One pass over dy and x produces dx and the per-row-block partial sums
+ * (ws = sn_bn_workspace_bytes(M, C), fixed summation order, no atomics), a small finalize adds them into dgamma / dbeta.
+ * dx == NULL: parameter gradients only; dgamma == dbeta == NULL: dx only (mean, var, ws unused).  scale / shift as
+ * sn_bn_global_scale_shift wrote them; mean / var are read, never written. */
+int sn_bn_frozen_backward(const void *dy, const void *x, const void *accumulate, void *dx, int M, int C, int ps_dy, int ps_x,
+                          int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean, const float *var,
+                          float eps, int relu, void *ws, float *dgamma, float *dbeta, sn_stream_t stream);
+/* sn_bn_global_scale_shift for a table of layers in one launch; bit-equal results.  desc: n_desc records of 56 bytes on the
+ * device, {const float *gamma (NULL = 1), *beta, *mean, *var; float *scale, *shift; int C; float eps}. */
+int sn_bn_global_scale_shift_batch(const void *desc, int n_desc, sn_stream_t stream);
 
 /* Depthwise 3x3 convolution (Convolution with num_group == channels; mobilenetv2_e2e.py:27-43,57-66), channels-last
  * fp16, weights [C][KH*KW] fp16.  dgrad adds `accumulate` (may be NULL / alias dx); wgrad accumulates (+=) into fp32

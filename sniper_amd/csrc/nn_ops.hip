@@ -62,6 +62,7 @@ SN_EXPORT int sn_pack_stem_input(const float *x_nchw, void *out, int N, int C, i
 //   bn_finalize : mean/var -> scale = gamma*invstd, shift = beta - mean*scale; running stats
 //   bn_apply    : y = act(x*scale + shift), act = none / relu / relu6 (`relu` argument 0 / 1 / 2)
 //   bn_bwd_reduce / bn_bwd_dx : gradients through (ReLU o BN) in training mode
+//   bn_frozen_bwd : the same through a moving-statistics layer of a training graph (fix_bn): constant statistics, one pass
 // BatchNorm(fix_gamma=False, eps=2e-5, momentum) call sites: resnet_mx_101_e2e.py:38-58.
 // ---------------------------------------------------------------------------------------------
 constexpr int kBnThreads = 256;
@@ -227,15 +228,36 @@ __global__ __launch_bounds__(kBnFinThreads) void bn_finalize_kernel(const float 
 }
 
 // scale/shift from running statistics (use_global_stats=True)
+__device__ __forceinline__ void bn_global_channel(const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                  const float *__restrict__ mean, const float *__restrict__ var, int c, float eps,
+                                                  float *__restrict__ scale, float *__restrict__ shift) {
+  const float invstd = 1.f / sqrtf(var[c] + eps);
+  const float g = gamma ? gamma[c] : 1.f;
+  scale[c] = g * invstd;
+  shift[c] = beta[c] - mean[c] * g * invstd;
+}
 __global__ void bn_global_kernel(const float *__restrict__ gamma, const float *__restrict__ beta,
                                  const float *__restrict__ mean, const float *__restrict__ var, int C, float eps,
                                  float *__restrict__ scale, float *__restrict__ shift) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float invstd = 1.f / sqrtf(var[c] + eps);
-  const float g = gamma ? gamma[c] : 1.f;
-  scale[c] = g * invstd;
-  shift[c] = beta[c] - mean[c] * g * invstd;
+  bn_global_channel(gamma, beta, mean, var, c, eps, scale, shift);
+}
+
+// The same for a table of layers in ONE launch (the trainable moving-statistics layers of a fix_bn graph after every optimizer
+// step: 90 launches of a few hundred bytes each for R101 otherwise).  desc[k] = {gamma (may be NULL), beta, mean, var, scale,
+// shift, C, eps}; one workgroup per layer (C <= 2048 in every graph: at most 8 channels per thread).
+struct BnGlobalDesc {
+  const float *gamma, *beta, *mean, *var;
+  float *scale, *shift;
+  int C;
+  float eps;
+};
+static_assert(sizeof(BnGlobalDesc) == 56, "BnGlobalDesc layout is part of the C ABI (sn_bn_global_scale_shift_batch)");
+
+__global__ __launch_bounds__(256) void bn_global_batch_kernel(const BnGlobalDesc *__restrict__ desc) {
+  const BnGlobalDesc d = desc[blockIdx.x];
+  for (int c = threadIdx.x; c < d.C; c += 256) bn_global_channel(d.gamma, d.beta, d.mean, d.var, c, d.eps, d.scale, d.shift);
 }
 
 __global__ __launch_bounds__(256) void bn_apply_kernel(const half_t *__restrict__ x, half_t *__restrict__ y, int M, int C,
@@ -522,6 +544,153 @@ SN_EXPORT int sn_bn_backward_blocks(const float *partials, int nblk, const void 
                        mean, invstd, (const float *)fin + C, (const float *)fin, relu);
     SN_CHECK_LAUNCH();
   }
+  return SN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Backward of y = act(x * scale + shift) with CONSTANT statistics (use_global_stats=True in a training graph: fix_bn,
+// resnet_mx_101_e2e.py:52-55).  dx = scale * g [+ acc] depends on nothing but the element and its channel, so the sums
+// for dbeta = sum g, dgamma = invstd * sum g * (x - mean) and dx come out of ONE pass over dy and x (the batch-statistics
+// backward reads both twice).  kDx / kPar select what the pass produces; with kPar the row-block count is the reduction
+// kernels' (partials in ws), without it the dx kernel's.
+// ---------------------------------------------------------------------------------------------
+// The fp32 value as the compiler must take it: without this the conversion to fp16 that follows an fma is folded into
+// v_fma_mixlo_f16 in some loops (ONE rounding) and left as fma + convert in others (two) -- dx would depend on which loop of which
+// variant handled the row, and the dx-only call would not reproduce the combined one bit for bit.
+__device__ __forceinline__ float bn_opaque(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+
+template <bool kDx, bool kPar>
+__global__ __launch_bounds__(kBnThreads) void bn_frozen_bwd_kernel(const half_t *__restrict__ dy, const half_t *__restrict__ x,
+                                                                   const half_t *__restrict__ acc, half_t *__restrict__ dx, int M,
+                                                                   int C, int ps_dy, int ps_x, int ps_acc, int ps_dx,
+                                                                   int rows_per_block, const float *__restrict__ scale,
+                                                                   const float *__restrict__ shift, const float *__restrict__ mean,
+                                                                   int relu, float *__restrict__ part) {
+  const BnMap m = bn_map(C);
+  if (!kPar && !m.on) return;
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
+  float s[8], q[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+  if (m.on) {
+    float sc[8], sh[8], mu[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = m.chunk * 8 + j;
+      sc[j] = scale[c]; sh[j] = shift[c]; mu[j] = kPar ? mean[c] : 0.f;
+    }
+    const half_t *pg = dy + m.chunk * 8, *px = x + m.chunk * 8, *pa = (kDx && acc) ? acc + m.chunk * 8 : nullptr;
+    half_t *po = kDx ? dx + m.chunk * 8 : nullptr;
+    auto body = [&](const half8 &g, const half8 &v, const half8 &a, size_t r) {
+      half8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xf = (float)v[j];
+        float gf = (float)g[j];
+        if (!bn_act_pass(bn_affine(xf, sc[j], sh[j]), relu)) gf = 0.f;
+        if (kPar) {
+          s[j] += gf;
+          q[j] += gf * (xf - mu[j]);
+        }
+        if (kDx) o[j] = (half_t)bn_opaque(__fmaf_rn(sc[j], gf, (float)a[j]));
+      }
+      if (kDx) *reinterpret_cast<half8 *>(po + r * ps_dx) = o;
+    };
+    // (zeros as a VALUE: `pa ? *p : zero` would become a load through a selected address, with `zero` in scratch memory)
+    auto load_acc = [&](size_t rr) {
+      half8 a = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (pa) a = *reinterpret_cast<const half8 *>(pa + rr * ps_acc);
+      return a;
+    };
+    int r = r0 + m.rl;
+    for (; r + (kBnUnroll - 1) * m.rpp < r1; r += kBnUnroll * m.rpp) {
+      half8 g[kBnUnroll], v[kBnUnroll], a[kBnUnroll];
+#pragma unroll
+      for (int u = 0; u < kBnUnroll; ++u) {
+        const size_t rr = (size_t)(r + u * m.rpp);
+        g[u] = *reinterpret_cast<const half8 *>(pg + rr * ps_dy);
+        v[u] = *reinterpret_cast<const half8 *>(px + rr * ps_x);
+        a[u] = load_acc(rr);
+      }
+#pragma unroll
+      for (int u = 0; u < kBnUnroll; ++u) body(g[u], v[u], a[u], (size_t)(r + u * m.rpp));
+    }
+    for (; r < r1; r += m.rpp)
+      body(*reinterpret_cast<const half8 *>(pg + (size_t)r * ps_dy), *reinterpret_cast<const half8 *>(px + (size_t)r * ps_x),
+           load_acc((size_t)r), (size_t)r);
+  }
+  if (kPar) {
+    float *po = part + (size_t)blockIdx.x * 2 * C;  // [row block][sum g | sum g*(x-mean)][C]
+    bn_block_reduce(m, C, s, q, [&](int c, int j, float a) { po[(j < 8 ? 0 : C) + c] = a; });
+  }
+}
+
+// partials -> dbeta += sum g, dgamma += invstd * sum g*(x-mean), invstd from the moving variance as bn_global_kernel has it
+__global__ __launch_bounds__(kBnFinThreads) void bn_frozen_finalize_kernel(const float *__restrict__ part, int nblk, int C,
+                                                                           const float *__restrict__ var, float eps,
+                                                                           float *__restrict__ dgamma, float *__restrict__ dbeta) {
+  const int c0 = blockIdx.x * 32 + (threadIdx.x & 31);      // (inputs first: see bn_finalize_kernel)
+  const bool head = threadIdx.x < 32 && c0 < C;
+  float vr = 1.f, db0 = 0.f, dg0 = 0.f;
+  if (head) {
+    vr = var[c0];
+    if (dbeta) db0 = dbeta[c0];
+    if (dgamma) dg0 = dgamma[c0];
+  }
+  double sg, sgx;
+  int c;
+  bn_sum_partials(part, nblk, C, sg, sgx, c);
+  if (!head) return;
+  const float is = 1.f / sqrtf(vr + eps);
+  if (dbeta) dbeta[c] = db0 + (float)sg;
+  if (dgamma) dgamma[c] = dg0 + (float)(sgx * (double)is);
+}
+
+// dx (may be NULL) and / or dgamma, dbeta (each may be NULL; accumulated, +=) of a moving-statistics layer; scale / shift as
+// sn_bn_global_scale_shift wrote them, mean / var the moving statistics, ws = sn_bn_workspace_bytes(M, C) (unused and may be
+// NULL when neither parameter gradient is wanted).  One pass (+ a finalize of the partials), no atomics.
+SN_EXPORT int sn_bn_frozen_backward(const void *dy, const void *x, const void *accumulate, void *dx, int M, int C, int ps_dy,
+                                    int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean,
+                                    const float *var, float eps, int relu, void *ws, float *dgamma, float *dbeta,
+                                    sn_stream_t stream) {
+  const bool par = dgamma || dbeta;
+  SN_REQUIRE(dy && x && scale && shift && bn_shape_ok(C) && M > 0 && (dx || par) && (!par || (mean && var && ws)) &&
+                 ps_dy >= C && ps_x >= C && (!dx || ps_dx >= C) && (!(dx && accumulate) || ps_acc >= C),
+             "sn_bn_frozen_backward: bad arguments (C=%d)", C);
+  hipStream_t s = sn_stream(stream);
+  int rows_per_block;
+  if (!par) {
+    const dim3 grid = bn_grid(M, C, 8192, &rows_per_block);
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<true, false>), grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x,
+                       (const half_t *)accumulate, (half_t *)dx, M, C, ps_dy, ps_x, ps_acc, ps_dx, rows_per_block, scale, shift,
+                       mean, relu, (float *)nullptr);
+    SN_CHECK_LAUNCH();
+    return SN_OK;
+  }
+  float *part = (float *)ws + 2 * C;      // (the layout of sn_bn_backward's workspace: the first 2C floats are its `fin`)
+  const dim3 grid = bn_grid(M, C, bn_reduce_cap(C), &rows_per_block);
+  if (dx)
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<true, true>), grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x,
+                       (const half_t *)accumulate, (half_t *)dx, M, C, ps_dy, ps_x, ps_acc, ps_dx, rows_per_block, scale, shift,
+                       mean, relu, part);
+  else
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<false, true>), grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x,
+                       (const half_t *)nullptr, (half_t *)nullptr, M, C, ps_dy, ps_x, 0, 0, rows_per_block, scale, shift, mean,
+                       relu, part);
+  SN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(bn_frozen_finalize_kernel, dim3(sn_div_up(C, 32)), dim3(kBnFinThreads), 0, s, (const float *)part, (int)grid.x,
+                     C, var, eps, dgamma, dbeta);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
+SN_EXPORT int sn_bn_global_scale_shift_batch(const void *desc, int n_desc, sn_stream_t stream) {
+  SN_REQUIRE(desc && n_desc > 0, "sn_bn_global_scale_shift_batch: bad arguments");
+  hipLaunchKernelGGL(bn_global_batch_kernel, dim3(n_desc), dim3(256), 0, sn_stream(stream), (const BnGlobalDesc *)desc);
+  SN_CHECK_LAUNCH();
   return SN_OK;
 }
 

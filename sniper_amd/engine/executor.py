@@ -251,6 +251,7 @@ class Executor(object):
         self._const = {}
         self._bn_cache_valid = False
         self._wt_tables = {}
+        self._bn_table = None
         self.num_update = 0
         self._lower()
         self._mark_half_region()
@@ -695,10 +696,29 @@ class Executor(object):
                 hip.call('sn_copy2d', p.master, p.w16, 1, p.numel, p.numel, p.numel, 1, 0, hip.stream())
         self._transpose_weights(only_trainable)
         self._bn_cache_valid = False
+        self._refresh_bn_table()
         for s in self.steps:
             s.params_changed(only_trainable)
         if not self.for_training:
             self.fold_store['__valid__'] = True
+
+    def _refresh_bn_table(self):
+        """scale / shift of every moving-statistics BatchNorm whose gamma / beta train (fix_bn graphs), from the fp32 masters, in
+        one sn_bn_global_scale_shift_batch launch over a device-resident descriptor table (built once: the buffers never move,
+        and the optimizer graph captures the launch).  No such layer -- every graph without fix_bn -- no launch."""
+        tab = self._bn_table
+        if tab is None:
+            bns = [s for s in self.steps if getattr(s, 'batched_refresh', None) is not None and s.batched_refresh()]
+            rec = np.zeros(len(bns), dtype=np.dtype([('gamma', '<u8'), ('beta', '<u8'), ('mean', '<u8'), ('var', '<u8'),
+                                                    ('scale', '<u8'), ('shift', '<u8'), ('C', '<i4'), ('eps', '<f4')]))
+            assert rec.dtype.itemsize == 56
+            for k, s in enumerate(bns):
+                rec[k] = (0 if s.fix_gamma else s.gamma.master.data_ptr(), s.beta.master.data_ptr(), s.mean.data_ptr(),
+                          s.var.data_ptr(), s.scale.data_ptr(), s.shift.data_ptr(), s.C, s.eps)
+            dev = torch.from_numpy(rec.view(np.uint8).copy()).to(self.device) if len(bns) else None
+            tab = self._bn_table = (dev, len(bns), bns)        # steps kept: they own the tensors behind the pointers
+        if tab[1]:
+            hip.call('sn_bn_global_scale_shift_batch', tab[0], tab[1], hip.stream())
 
     def derived_buffer(self, key, shape, dtype):
         """Test time: a buffer DERIVED from the parameters alone (a BatchNorm's scale / shift from its moving statistics) -- one per

@@ -96,9 +96,11 @@ class BatchNormStep(Step):
         self.beta = ex.register_param(self.pname('beta'))
         if self.fix_gamma:
             self.gamma.trainable = False
-        if self.global_stats:
-            # moving-statistics BN layers carry no gradient here: in every SNIPER config they are frozen
-            # (network.FIXED_PARAMS) -- bn_data's beta, the one exception by name, is frozen too
+        # image input (C <= 4): folded into the stem convolution's input packing
+        self.is_stem = self.x.fmt == 'f32' and len(self.x.shape) == 4 and C <= 4
+        if self.is_stem:
+            # bn_data (fix_gamma, moving statistics): its beta is no FIXED_PARAMS name in any config, and it is frozen all the
+            # same.  Every other moving-statistics layer trains what the fixed names leave trainable (fix_bn).
             self.gamma.trainable = self.beta.trainable = False
         self.mean = ex.register_aux(self.pname('moving_mean'))
         self.var = ex.register_aux(self.pname('moving_var'))
@@ -109,8 +111,6 @@ class BatchNormStep(Step):
         self.shift = ex.derived_buffer(('bn_shift', self.node.name), (C,), F32)
         self.save_mean, self.save_invstd = ex.empty((C,), F32), ex.empty((C,), F32)
         self.bws = None
-        # image input (C <= 4): folded into the stem convolution's input packing
-        self.is_stem = self.x.fmt == 'f32' and len(self.x.shape) == 4 and C <= 4
         cons = ex.consumers.get((id(self.node), 0), [])
         self.relu = (not self.is_stem and len(cons) == 1 and cons[0].op == 'Activation' and
                      cons[0].attrs.get('act_type') == 'relu')
@@ -126,7 +126,8 @@ class BatchNormStep(Step):
         self.folded_into = None
         prod = None if self.is_stem else self.x.producer
         is_conv = prod is not None and type(prod).__name__ == 'ConvolutionStep' and self.x.fmt == 'act'
-        frozen_pair = (ex.for_training and is_conv and self.global_stats and not prod.w.trainable
+        frozen_pair = (ex.for_training and is_conv and self.global_stats and not self.gamma.trainable and not self.beta.trainable
+                       and not prod.w.trainable
                        and (prod.b is None or not prod.b.trainable) and not prod.x.needs_grad
                        and os.environ.get('SNIPER_TRAIN_FOLD_BN', '1') != '0')
         if (is_conv and (not ex.for_training or frozen_pair) and self.act in (0, 1)
@@ -176,7 +177,16 @@ class BatchNormStep(Step):
                 if got is not None:
                     self.stats_from = got
 
+    def batched_refresh(self):
+        """A moving-statistics layer of a training graph whose gamma / beta train (fix_bn): scale / shift follow every optimizer
+        step, through the executor's ONE sn_bn_global_scale_shift_batch launch over all such layers (Executor._refresh_bn_table,
+        inside the captured optimizer pass) instead of a launch per layer."""
+        return self.ex.for_training and self.global_stats and (self.gamma.trainable or self.beta.trainable)
+
     def params_changed(self, only_trainable=False):
+        if self.batched_refresh():
+            self._global_ready = True          # (the executor's table launch ran just before the steps are told)
+            return
         # after an optimizer step only trainable parameters moved; a moving-statistics layer with frozen
         # gamma/beta keeps its folded scale/shift
         if not (only_trainable and self.global_stats and not self.gamma.trainable and not self.beta.trainable):
@@ -246,10 +256,6 @@ class BatchNormStep(Step):
         ex = self.ex
         if self.y.grad is None or not self.y.needs_grad:
             return
-        if not self._use_batch_stats():
-            if self.x.needs_grad or self.gamma.trainable or self.beta.trainable:
-                raise NotImplementedError('gradient through a use_global_stats BatchNorm (%s)' % self.node.name)
-            return
         n, h, w, c = self.x.nhwc()
         M = n * h * w
         x = ex.as_act(self.x)
@@ -258,7 +264,16 @@ class BatchNormStep(Step):
             dx, acc = ex.grad_slot(self.x) if self.x.fmt == 'act' else (ex.empty(x.shape, F16), None)
         dg = self.gamma.grad if self.gamma.trainable else None
         db = self.beta.grad if self.beta.trainable else None
-        if self.bwd_partials is not None:       # sum g, sum g*(x-mean) came out of the consumer's data-gradient epilogue
+        if not self._use_batch_stats():
+            # constant statistics: dx = scale * g, dbeta = sum g, dgamma = invstd * sum g * (x - moving_mean) -- one pass
+            ws = None
+            if dg is not None or db is not None:
+                if self.bws is None:
+                    self.bws = ex.empty((hip.query('sn_bn_workspace_bytes', M, c),), torch.uint8)
+                ws = self.bws
+            hip.call('sn_bn_frozen_backward', self.y.grad, x, acc, dx, M, c, c, c, c, c, self.scale, self.shift, self.mean,
+                     self.var, self.eps, self.act, ws, dg, db, hip.stream())
+        elif self.bwd_partials is not None:       # sum g, sum g*(x-mean) came out of the consumer's data-gradient epilogue
             part, nblk = self.bwd_partials
             self.bwd_partials = None
             hip.call('sn_bn_backward_blocks', part, nblk, self.y.grad, x, acc, dx, M, c, c, c, c, c, self.scale,

@@ -44,6 +44,8 @@ def inverted_residual_unit(data, num_in_filter, num_filter, ifshortcut, stride, 
 
 class mobilenetv2_e2e(Symbol):
     def __init__(self, n_proposals=400, momentum=0.95, fix_bn=False, test_nbatch=1):
+        """`fix_bn` is accepted and ignored, as the reference's class does (mobilenetv2_e2e.py:37 there): every BatchNorm of
+        this network normalises with batch statistics whatever the flag says."""
         Symbol.__init__(self)
         self.multiplier = 1
         self.test_nbatch = test_nbatch
