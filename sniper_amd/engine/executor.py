@@ -253,6 +253,12 @@ class Executor(object):
         self._wt_tables = {}
         self._bn_table = None
         self.num_update = 0
+        self._var_index = None        # _var_node: variable name -> node, built at the first lookup
+        self.outputs = None           # _forward_body: the heads as fp32 reference-order tensors
+        self.capture_first = False    # Module._exe_for: every derived buffer was adopted, capture at the first forward
+        self._capture_stream = None   # forward: the side stream the test-time forward is captured on
+        self._pinned_inputs = {}      # load_inputs: input name -> ring of pinned host buffers
+        self._hyper_host = None       # update: the values self.hyper holds
         self._lower()
         self._mark_half_region()
         self.split_k = self._choose_split() if (split_backward and for_training) else 0
@@ -263,13 +269,13 @@ class Executor(object):
         # torch's stream, which is the stream every C-ABI call is given) and replayed; the gradient all-reduce runs
         # between the two.  Hyper-parameters that change per step live in `self.hyper` on the device.
         self.hyper = self.zeros((4,), F32)      # lr, wd, momentum, rescale_grad
-        self.use_graphs = (for_training and os.environ.get('SNIPER_HIP_GRAPHS', '1') != '0' and
-                           not any(type(st).__name__ == 'CustomStep' for st in self.steps))
+        from .ops import CustomStep
+        graphs = os.environ.get('SNIPER_HIP_GRAPHS', '1') != '0' and not any(isinstance(st, CustomStep) for st in self.steps)
+        self.use_graphs = for_training and graphs
         self.graph_warmup = 2
         # Inference executors (one per input shape, kept by the Module) replay a captured forward from their third call on:
         # an eager test-time forward is ~250 launches per batch from Python, host-bound at the finer AutoFocus scales.
-        self.use_infer_graphs = (not for_training and os.environ.get('SNIPER_HIP_GRAPHS', '1') != '0' and
-                                 not any(type(st).__name__ == 'CustomStep' for st in self.steps))
+        self.use_infer_graphs = not for_training and graphs
         self._infer_graph, self._infer_calls = None, 0
         self._keepalive = []
         # Weight gradients are DEFERRED and launched as tables of layers (sn_conv_wgrad_batch): one stage-3 layer has 16-36
@@ -317,17 +323,26 @@ class Executor(object):
         return [self.vals[(id(n), i)] for n, i in node.inputs]
 
     # ---- format conversion (forward) ----------------------------------------------------------
+    def relayout(self, src, dst, nhwc, to_nchw, pitch=None):
+        """One (n, h, w, c) tensor between channels-last and reference (n, c, h, w) order, src -> dst; fp16 / fp32 as the two tensors'
+        dtypes say.  to_nchw: src is the channels-last side.  pitch: channel pitch of the channels-last side where it is padded."""
+        n, h, w, c = nhwc
+        hw, cp = h * w, pitch or c
+        s32, d32 = int(src.dtype == F32), int(dst.dtype == F32)
+        if hw == 1:
+            hip.call('sn_copy2d', src, dst, n, c, cp if to_nchw else c, c if to_nchw else cp, s32, d32, hip.stream())
+        elif to_nchw:
+            hip.call('sn_transpose_batched', src, dst, n, hw, c, hw * cp, c * hw, cp, hw, s32, d32, hip.stream())
+        else:
+            hip.call('sn_transpose_batched', src, dst, n, c, hw, c * hw, hw * cp, hw, cp, s32, d32, hip.stream())
+
     def as_f32(self, v):
         """fp32 reference-order view of a Val (converted copy cached per forward)."""
         if v.fmt == 'f32':
             return v.t
         if v.alt is None:
-            n, h, w, c = v.nhwc()
             out = self.empty(v.shape, F32)
-            if h * w == 1:
-                hip.call('sn_copy2d', v.t, out, n, c, c, c, 0, 1, hip.stream())
-            else:
-                hip.call('sn_transpose_batched', v.t, out, n, h * w, c, h * w * c, c * h * w, c, h * w, 0, 1, hip.stream())
+            self.relayout(v.t, out, v.nhwc(), True)
             if v.chan_perm is not None:      # (a head / a test reading a group-major map: back to the reference's channel order)
                 inv = np.empty(len(v.chan_perm), np.int64)
                 inv[np.asarray(v.chan_perm)] = np.arange(len(v.chan_perm))
@@ -339,12 +354,8 @@ class Executor(object):
         if v.fmt == 'act':
             return v.t
         if v.alt is None:
-            n, h, w, c = v.nhwc()
-            out = self.empty((n, h, w, c), F16)
-            if h * w == 1:
-                hip.call('sn_copy2d', v.t, out, n, c, c, c, 1, 0, hip.stream())
-            else:
-                hip.call('sn_transpose_batched', v.t, out, n, c, h * w, c * h * w, h * w * c, h * w, c, 1, 0, hip.stream())
+            out = self.empty(v.nhwc(), F16)
+            self.relayout(v.t, out, v.nhwc(), False)
             v.alt = out
         return v.alt
 
@@ -361,7 +372,7 @@ class Executor(object):
         # copy on write: the tensor is also the (not yet consumed) gradient of the residual add's other operand.  In ResNet /
         # MobileNetV2 that operand's producer has run its backward and dropped the tensor by now (no copy); any other
         # graph order gets a private copy instead of a silently corrupted dY.
-        group = getattr(v, 'grad_group', None)
+        group = v.grad_group
         if group is not None:
             v.grad_group = None
             ptr = v.grad.data_ptr()
@@ -373,6 +384,17 @@ class Executor(object):
             v.grad = self.empty(src.shape, src.dtype)
             return v.grad, src
         return v.grad, v.grad
+
+    def input_grad_dst(self, v):
+        """-> (dx, acc) for a step that writes the gradient of its input v as channels-last fp16: v's own slot (grad_slot) when v is
+        an activation, else a temporary that input_grad_done converts and accumulates."""
+        if v.fmt == 'act':
+            return self.grad_slot(v)
+        return self.empty(v.nhwc(), F16), None
+
+    def input_grad_done(self, v, dx):
+        if v.fmt != 'act':
+            self.add_grad(v, dx, 'act')
 
     def queue_wgrad(self, *problem):
         """problem = the arguments of sn_conv_wgrad up to `dil` (tensors dy, x, dw first)."""
@@ -403,18 +425,8 @@ class Executor(object):
             return
         n, h, w, c = v.nhwc()
         if g_fmt != v.fmt:
-            if v.fmt == 'act':   # f32 NCHW -> act
-                conv = self.empty((n, h, w, c), F16)
-                if h * w == 1:
-                    hip.call('sn_copy2d', g, conv, n, c, c, c, 1, 0, hip.stream())
-                else:
-                    hip.call('sn_transpose_batched', g, conv, n, c, h * w, c * h * w, h * w * c, h * w, c, 1, 0, hip.stream())
-            else:
-                conv = self.empty(v.shape, F32)
-                if h * w == 1:
-                    hip.call('sn_copy2d', g, conv, n, c, c, c, 0, 1, hip.stream())
-                else:
-                    hip.call('sn_transpose_batched', g, conv, n, h * w, c, h * w * c, c * h * w, c, h * w, 0, 1, hip.stream())
+            conv = self.empty((n, h, w, c), F16) if v.fmt == 'act' else self.empty(v.shape, F32)
+            self.relayout(g, conv, (n, h, w, c), v.fmt != 'act')
             g = conv
         if v.grad is None:
             v.grad = g
@@ -650,7 +662,7 @@ class Executor(object):
                         self.params[n.name].half_region = True
 
     def _var_node(self, name):
-        idx = self.__dict__.get('_var_index')
+        idx = self._var_index
         if idx is None:                     # (a linear search per parameter was a fifth of a test-time bind: 336 x 700 nodes)
             idx = self._var_index = {}
             for n in self.nodes:
@@ -708,7 +720,7 @@ class Executor(object):
         and the optimizer graph captures the launch).  No such layer -- every graph without fix_bn -- no launch."""
         tab = self._bn_table
         if tab is None:
-            bns = [s for s in self.steps if getattr(s, 'batched_refresh', None) is not None and s.batched_refresh()]
+            bns = [s for s in self.steps if s.batched_refresh()]
             rec = np.zeros(len(bns), dtype=np.dtype([('gamma', '<u8'), ('beta', '<u8'), ('mean', '<u8'), ('var', '<u8'),
                                                     ('scale', '<u8'), ('shift', '<u8'), ('C', '<i4'), ('eps', '<f4')]))
             assert rec.dtype.itemsize == 56
@@ -802,7 +814,7 @@ class Executor(object):
                         # host inputs (the reference iterator's small arrays -- valid ranges, im_info -- or whole host batches) go
                         # through a ring of pinned buffers: a copy from PAGEABLE memory is synchronous, i.e. the host would wait
                         # for the step in flight before it could enqueue this one (13 ms per batch, profiles/r05_fit_path.txt)
-                        ring = self.__dict__.setdefault('_pinned_inputs', {}).setdefault(node.name, {'k': 0, 'bufs': [], 'evs': []})
+                        ring = self._pinned_inputs.setdefault(node.name, {'k': 0, 'bufs': [], 'evs': []})
                         if len(ring['bufs']) < 3:
                             ring['bufs'].append(torch.empty(tuple(src.shape), dtype=torch.float32, pin_memory=True))
                             ring['evs'].append(None)
@@ -829,7 +841,7 @@ class Executor(object):
                     hip.call('sn_copy2d', src, v.t, 1, n, n, n, 1, 1, hip.stream())
                 else:
                     v.t.copy_(src, non_blocking=True)
-                    ring = getattr(self, '_pinned_inputs', {}).get(node.name)
+                    ring = self._pinned_inputs.get(node.name)
                     if ring is not None and ring.pop('pending', None) is not None and src.is_pinned():
                         ev = torch.cuda.Event()
                         ev.record()
@@ -855,7 +867,7 @@ class Executor(object):
             self._infer_calls += 1
             # the first call runs eagerly (lazy allocations, parameter packing) -- unless this executor adopted every derived buffer of its
             # Module (Module._exe_for: capture_first): then a new batch shape costs bind + capture, not bind + eager pass + capture
-            if (self._infer_calls > 1 or getattr(self, 'capture_first', False)) and _CAPTURE_ALLOWED:
+            if (self._infer_calls > 1 or self.capture_first) and _CAPTURE_ALLOWED:
                 import gc
                 gc.collect()
                 gc_was = gc.isenabled()
@@ -867,8 +879,7 @@ class Executor(object):
                     # first call already made every lazy allocation, so nothing here needs freed memory.
                     g = torch.cuda.CUDAGraph()
                     cur = torch.cuda.current_stream()
-                    side = self.__dict__.setdefault('_capture_stream', None) or torch.cuda.Stream(device=self.device)
-                    self._capture_stream = side
+                    side = self._capture_stream = self._capture_stream or torch.cuda.Stream(device=self.device)
                     side.wait_stream(cur)
                     with torch.cuda.stream(side):
                         g.capture_begin(capture_error_mode='thread_local')
@@ -1005,7 +1016,7 @@ class Executor(object):
         # with the value as a launch argument, and only when they change: a host-to-device copy from pageable memory makes
         # the host wait for everything already queued on the stream, i.e. for the whole previous step.
         vals = (float(lr), float(wd), float(momentum), float(rescale_grad))
-        last = getattr(self, '_hyper_host', None)
+        last = self._hyper_host
         for i, v in enumerate(vals):
             if last is None or last[i] != v:
                 hip.call('sn_ew_f32', None, None, self.hyper[i:], 1, 4, v, hip.stream())

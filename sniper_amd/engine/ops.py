@@ -73,9 +73,27 @@ class Step(object):
         """Executor.adopt_derived: True when this step needs nothing recomputed on a shape that shares its parameters"""
         return True
 
+    def batched_refresh(self):
+        """Executor._refresh_bn_table: True for a step whose derived buffers the executor's one table launch keeps current"""
+        return False
+
     def transpose_jobs(self, only_trainable=False):
         """extra (master, dst, O, T, I) transposed weight copies this step needs (Executor.transpose_jobs)"""
         return []
+
+
+def gemm_geom(M, K, O):
+    """The 13 geometry arguments of the implicit-GEMM entry points (N, H, W, C, in pitch, O, out pitch, residual pitch, KH, KW, stride,
+    pad, dil) for a plain (M, K) x (K, O) product: a 1x1 convolution over M pixels."""
+    return (M, 1, 1, K, K, O, O, 0, 1, 1, 1, 0, 1)
+
+
+def _conv_behind(v):
+    """The ConvolutionStep whose epilogue writes Val v -- its producer, or the convolution that absorbed the residual add that is -- or None."""
+    st = v.producer
+    if isinstance(st, BinaryStep):
+        st = st.fused_conv
+    return st if isinstance(st, ConvolutionStep) else None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -111,6 +129,8 @@ class BatchNormStep(Step):
         self.shift = ex.derived_buffer(('bn_shift', self.node.name), (C,), F32)
         self.save_mean, self.save_invstd = ex.empty((C,), F32), ex.empty((C,), F32)
         self.bws = None
+        self._global_ready = False       # scale / shift hold the folded moving statistics (fold_global, params_changed, adopt_derived)
+        self.bwd_partials = None         # ConvolutionStep.launch_dgrad: (partials, blocks) of this layer's backward sums, for one backward
         cons = ex.consumers.get((id(self.node), 0), [])
         self.relu = (not self.is_stem and len(cons) == 1 and cons[0].op == 'Activation' and
                      cons[0].attrs.get('act_type') == 'relu')
@@ -125,7 +145,7 @@ class BatchNormStep(Step):
         # either side, so the pass over the 128 x 128 / 256 x 256 maps (the largest tensors of the step) disappears.
         self.folded_into = None
         prod = None if self.is_stem else self.x.producer
-        is_conv = prod is not None and type(prod).__name__ == 'ConvolutionStep' and self.x.fmt == 'act'
+        is_conv = isinstance(prod, ConvolutionStep) and self.x.fmt == 'act'
         frozen_pair = (ex.for_training and is_conv and self.global_stats and not self.gamma.trainable and not self.beta.trainable
                        and not prod.w.trainable
                        and (prod.b is None or not prod.b.trainable) and not prod.x.needs_grad
@@ -144,9 +164,8 @@ class BatchNormStep(Step):
         self.dual_from = None
         if (not ex.for_training and self.folded_into is None and not self.is_stem and self.x.fmt == 'act' and self.act in (0, 1)
                 and os.environ.get('SNIPER_INFER_DUAL_BN', '1') != '0'):
-            src = self.x.producer
-            conv = getattr(src, 'fused_conv', None) if type(src).__name__ == 'BinaryStep' else src
-            if type(conv).__name__ == 'ConvolutionStep' and conv.request_dual(self):
+            conv = _conv_behind(self.x)
+            if conv is not None and conv.request_dual(self):
                 self.dual_from = conv
         if self.is_stem:
             self.y = self.new_out('f32', alloc=False)
@@ -158,30 +177,31 @@ class BatchNormStep(Step):
             self.y = self.new_out('act')
         self.y.needs_grad = ex.for_training and (self.x.needs_grad or self.gamma.trainable or self.beta.trainable) \
             and not self.is_stem
-        self._global_ready = False
         # the one operator that consumes this layer's (activated) output, if there is exactly one: its data gradient is then
         # the complete dL/dy and may carry the backward reduction in its epilogue (ConvolutionStep.launch_dgrad)
         chain = cons
         if self.act and len(cons) == 1:
             chain = ex.consumers.get((id(cons[0]), 0), [])
         self.sole_consumer = chain[0] if len(chain) == 1 else None
-        self.bwd_partials = None
         # batch statistics from the producing convolution's epilogue (plain conv -> BN, or the conv that absorbed the
         # residual add this BN reads): sn_conv_fwd_stats + sn_bn_finalize_blocks instead of sn_bn_stats + sn_bn_finalize
         self.stats_from = None
         if ex.for_training and not self.global_stats and not self.is_stem and self.x.fmt == 'act':
-            prod = self.x.producer
-            conv = getattr(prod, 'fused_conv', None) if type(prod).__name__ == 'BinaryStep' else prod
-            if type(conv).__name__ == 'ConvolutionStep':
-                got = conv.request_stats()
-                if got is not None:
-                    self.stats_from = got
+            conv = _conv_behind(self.x)
+            if conv is not None:
+                self.stats_from = conv.request_stats()
 
     def batched_refresh(self):
         """A moving-statistics layer of a training graph whose gamma / beta train (fix_bn): scale / shift follow every optimizer
         step, through the executor's ONE sn_bn_global_scale_shift_batch launch over all such layers (Executor._refresh_bn_table,
         inside the captured optimizer pass) instead of a launch per layer."""
         return self.ex.for_training and self.global_stats and (self.gamma.trainable or self.beta.trainable)
+
+    def fold_global(self):
+        """scale / shift from the moving statistics and the gamma / beta masters, into the persistent buffers"""
+        hip.call('sn_bn_global_scale_shift', None if self.fix_gamma else self.gamma.master, self.beta.master, self.mean, self.var,
+                 self.C, self.eps, self.scale, self.shift, hip.stream())
+        self._global_ready = True
 
     def params_changed(self, only_trainable=False):
         if self.batched_refresh():
@@ -196,10 +216,7 @@ class BatchNormStep(Step):
                 # back to Python, so a lazy recompute after set_params / a checkpoint load would keep the stale scale / shift.
                 # A test-time executor normalises EVERY layer with the moving statistics, whatever use_global_stats says
                 # (MobileNetV2's BatchNorm after the depthwise convolutions is neither global-stats nor folded).
-                g = None if self.fix_gamma else self.gamma.master
-                hip.call('sn_bn_global_scale_shift', g, self.beta.master, self.mean, self.var, self.C, self.eps, self.scale,
-                         self.shift, hip.stream())
-                self._global_ready = True
+                self.fold_global()
                 if self.folded_into is not None:
                     self.folded_into.refold(self.scale, self.shift)
 
@@ -227,9 +244,7 @@ class BatchNormStep(Step):
         g = None if self.fix_gamma else self.gamma.master
         if not self._use_batch_stats():
             if not self._global_ready:
-                hip.call('sn_bn_global_scale_shift', g, self.beta.master, self.mean, self.var, self.C, self.eps, self.scale,
-                         self.shift, hip.stream())
-                self._global_ready = True
+                self.fold_global()
             if self.is_stem:
                 return
         if self.is_stem:
@@ -259,9 +274,7 @@ class BatchNormStep(Step):
         n, h, w, c = self.x.nhwc()
         M = n * h * w
         x = ex.as_act(self.x)
-        dx, acc = (None, None)
-        if self.x.needs_grad:
-            dx, acc = ex.grad_slot(self.x) if self.x.fmt == 'act' else (ex.empty(x.shape, F16), None)
+        dx, acc = ex.input_grad_dst(self.x) if self.x.needs_grad else (None, None)
         dg = self.gamma.grad if self.gamma.trainable else None
         db = self.beta.grad if self.beta.trainable else None
         if not self._use_batch_stats():
@@ -281,8 +294,8 @@ class BatchNormStep(Step):
         else:
             hip.call('sn_bn_backward', self.y.grad, x, acc, dx, M, c, c, c, c, c, self.scale, self.shift,
                      self.save_mean, self.save_invstd, self.act, self.bws, dg, db, hip.stream())
-        if self.x.needs_grad and self.x.fmt != 'act':
-            ex.add_grad(self.x, dx, 'act')
+        if self.x.needs_grad:
+            ex.input_grad_done(self.x, dx)
         self.y.grad = None
 
 
@@ -313,13 +326,9 @@ class ActivationStep(Step):
         if self.fused or self.y.grad is None or not self.x.needs_grad:
             return
         n, h, w, c = self.x.nhwc()
-        if self.x.fmt == 'act':
-            dx, acc = self.ex.grad_slot(self.x)
-            hip.call('sn_ew_f16', self.y.grad, acc, self.y.t, dx, n * h * w, c, c, c, c, c, 2, hip.stream())
-        else:
-            tmp = self.ex.empty(self.y.t.shape, F16)
-            hip.call('sn_ew_f16', self.y.grad, None, self.y.t, tmp, n * h * w, c, c, c, c, c, 2, hip.stream())
-            self.ex.add_grad(self.x, tmp, 'act')
+        dx, acc = self.ex.input_grad_dst(self.x)
+        hip.call('sn_ew_f16', self.y.grad, acc, self.y.t, dx, n * h * w, c, c, c, c, c, 2, hip.stream())
+        self.ex.input_grad_done(self.x, dx)
         self.y.grad = None
 
 
@@ -362,14 +371,9 @@ class ClipStep(Step):
             return
         n, h, w, c = self.x.nhwc()
         x = self.ex.as_act(self.x)
-        if self.x.fmt == 'act':
-            dx, acc = self.ex.grad_slot(self.x)
-            hip.call('sn_clip_f16', self.y.grad, x, acc, dx, n * h * w, c, c, c, c, c, self.lo, self.hi, 1,
-                     hip.stream())
-        else:
-            tmp = self.ex.empty(self.y.t.shape, F16)
-            hip.call('sn_clip_f16', self.y.grad, x, None, tmp, n * h * w, c, c, c, c, c, self.lo, self.hi, 1, hip.stream())
-            self.ex.add_grad(self.x, tmp, 'act')
+        dx, acc = self.ex.input_grad_dst(self.x)
+        hip.call('sn_clip_f16', self.y.grad, x, acc, dx, n * h * w, c, c, c, c, c, self.lo, self.hi, 1, hip.stream())
+        self.ex.input_grad_done(self.x, dx)
         self.y.grad = None
 
 
@@ -399,6 +403,8 @@ class _GemmLike(Step):
 
     def setup(self):
         ex = self.ex
+        self.wf = self.bf = None          # refold / BatchNormStep.adopt_derived: BatchNorm-folded fp16 weights and fp32 bias
+        self._splitk_bytes = None         # first test-time forward: scratch bytes of the split-K launch (0: not split)
         self.x = self.data_in()
         self.setup_geom()
         self.w = ex.register_param(self.pname('weight'), self.wkind, self.fc_in, need_wT=False)
@@ -407,7 +413,7 @@ class _GemmLike(Step):
         self.y = self.new_out('f32' if self.out_f32 else 'act')
         wt = ex.for_training and (self.pname('weight') not in ex.fixed)
         self.y.needs_grad = ex.for_training and (self.x.needs_grad or wt)
-        if self.x.needs_grad and ex.for_training and not getattr(self, 'depthwise', False):
+        if self.x.needs_grad and ex.for_training and not self.depthwise:
             self.w.need_wT = True
         self.tmp_nhwc32 = None
         if self.out_f32 and self.Ho * self.Wo > 1:
@@ -419,7 +425,7 @@ class _GemmLike(Step):
         addresses)."""
         w = self.w.master.view(self.O, -1) * scale.view(-1, 1)
         b = shift if self.b is None else self.b.master * scale + shift
-        if getattr(self, 'wf', None) is None:
+        if self.wf is None:
             # one folded copy per Module: the executors of its other batch shapes fold the same masters with the same statistics
             ent = self.ex.fold_store.get(self.w.name) if self.w.name in self.ex.shared_names else None
             if ent is None or ent[0].shape != self.w.w16.shape:
@@ -437,9 +443,7 @@ class _GemmLike(Step):
         bias = self.b.master if self.b is not None else None
         self.launch_fwd(x, dst, bias)
         if self.tmp_nhwc32 is not None:
-            hw = self.Ho * self.Wo
-            hip.call('sn_transpose_batched', dst, self.y.t, self.N, hw, self.O, hw * self.O, self.O * hw, self.O, hw, 1, 1,
-                     hip.stream())
+            ex.relayout(dst, self.y.t, (self.N, self.Ho, self.Wo, self.O), True)
 
     def dy_act(self):
         """incoming gradient as channels-last fp16 with an 8-aligned channel pitch -> (tensor, pitch)"""
@@ -452,10 +456,8 @@ class _GemmLike(Step):
         dy = ex.zeros((self.N, self.Ho, self.Wo, Op), F16) if Op != self.O else ex.empty((self.N, self.Ho, self.Wo, Op), F16)
         if self.y.fmt == 'act':
             hip.call('sn_copy2d', g, dy, self.N * hw, self.O, self.O, Op, 0, 0, hip.stream())
-        elif hw == 1:
-            hip.call('sn_copy2d', g, dy, self.N, self.O, self.O, Op, 1, 0, hip.stream())
         else:
-            hip.call('sn_transpose_batched', g, dy, self.N, self.O, hw, self.O * hw, hw * Op, hw, Op, 1, 0, hip.stream())
+            ex.relayout(g, dy, (self.N, self.Ho, self.Wo, self.O), False, pitch=Op)
         return dy, Op
 
     def backward(self):
@@ -472,18 +474,23 @@ class _GemmLike(Step):
         if self.w.trainable or (self.b is not None and self.b.trainable):
             ex.on_side(param_grads, keep=(dy, x))
         if self.x.needs_grad:
-            if self.x.fmt == 'act':
-                dx, acc = ex.grad_slot(self.x)
-                self.launch_dgrad(dy, Op, acc, dx)
-            else:
-                dx = ex.empty(self.x_shape_nhwc(), F16)
-                self.launch_dgrad(dy, Op, None, dx)
-                ex.add_grad(self.x, dx, 'act')
+            dx, acc = ex.input_grad_dst(self.x)
+            self.launch_dgrad(dy, Op, acc, dx)
+            ex.input_grad_done(self.x, dx)
         self.y.grad = None
 
 
 @register('Convolution')
 class ConvolutionStep(_GemmLike):
+    def setup(self):
+        # fusions this convolution carries in its epilogue: attached by the steps lowered after it, read by the launches below
+        self.fused_residual = self.fused_dst = None      # BinaryStep.setup: the residual add's other operand and the add's output
+        self.fold_bn = None                              # BatchNormStep.setup: the BatchNorm (+ ReLU) folded into weights and bias
+        self.dual_bn = None                              # request_dual: the test-time BatchNorm written as the second output
+        self.stats_buf, self.stats_blocks = None, 0      # request_stats: per-row-tile sums for a batch-statistics BatchNorm
+        self.bnb_buf = None                              # launch_dgrad: backward sums of the BatchNorm below (_bn_below)
+        _GemmLike.setup(self)
+
     def setup_geom(self):
         a = self.a
         self.k = _tup(a['kernel'])
@@ -515,20 +522,21 @@ class ConvolutionStep(_GemmLike):
     def x_tensor(self):
         return None if self.is_stem else self.ex.as_act(self.x)
 
-    def x_shape_nhwc(self):
-        return (self.N, self.H, self.W, self.C)
+    def geom(self):
+        """The 13 geometry arguments of the implicit-GEMM forward entry points and their host-side queries (at call time: the residual
+        pitch follows fused_residual, attached after setup)."""
+        return (self.N, self.H, self.W, self.C, self.C, self.O, self.O, 0 if self.fused_residual is None else self.O, self.k[0],
+                self.k[1], self.s[0], self.p[0], self.d[0])
 
     def _stats_blocks(self):
         if self.is_stem or self.depthwise or self.out_f32:
             return 0
-        res = getattr(self, 'fused_residual', None)
-        return hip.query('sn_conv_fwd_stats_blocks', self.N, self.H, self.W, self.C, self.C, self.O, self.O,
-                         0 if res is None else self.O, self.k[0], self.k[1], self.s[0], self.p[0], self.d[0])
+        return hip.query('sn_conv_fwd_stats_blocks', *self.geom())
 
     def request_stats(self):
         """A batch-statistics BatchNorm reading this convolution's output (or the residual sum its epilogue writes) asks
         for the per-row-tile sums: -> (partials (blocks, 2, O) fp32, blocks) or None when the layer does not qualify."""
-        if getattr(self, 'stats_buf', None) is None:
+        if self.stats_buf is None:
             nblk = self._stats_blocks()
             if nblk <= 0:
                 return None
@@ -538,78 +546,75 @@ class ConvolutionStep(_GemmLike):
     def request_dual(self, bn):
         """A test-time moving-statistics BatchNorm (+ ReLU) that reads this convolution's output -- or the residual sum its
         epilogue writes -- and cannot fold into it asks to be written as the epilogue's second output.  -> accepted?"""
-        if (getattr(self, 'dual_bn', None) is not None or getattr(self, 'fold_bn', None) is not None or self.is_stem or
-                self.depthwise or self.out_f32 or self.ex.for_training):
+        if (self.dual_bn is not None or self.fold_bn is not None or self.is_stem or self.depthwise or self.out_f32 or
+                self.ex.for_training):
             return False
-        res = getattr(self, 'fused_residual', None)
-        if not hip.query('sn_conv_fwd_dual_ok', self.N, self.H, self.W, self.C, self.C, self.O, self.O, 0 if res is None else self.O,
-                         self.k[0], self.k[1], self.s[0], self.p[0], self.d[0], self.O):
+        if not hip.query('sn_conv_fwd_dual_ok', *self.geom(), self.O):
             return False
         self.dual_bn = bn
         return True
 
     def launch_fwd(self, x, dst, bias):
-        ex = self.ex
         if self.is_stem:
-            src, scale, shift = (self.x.stem if self.x.stem is not None else (self.x, None, None))
-            hip.call('sn_pack_stem_input', src.t, self.xp, self.N, self.C, self.H, self.W, self.Hp, self.Wp, self.p[0], self.p[1],
-                     scale, shift, hip.stream())
-            fold = getattr(self, 'fold_bn', None)
-            if fold is not None:     # frozen conv0 -> bn0 (-> relu0): the affine map rides in the weights / bias / epilogue (refold)
-                if getattr(self, 'wf', None) is None:
-                    raise RuntimeError('%s: folded BatchNorm weights missing (parameters were never set)' % self.node.name)
-                hip.call('sn_conv_stem_fwd', self.xp, self.wf, self.bf, dst, self.N, self.Hp, self.Wp, self.Ho, self.Wo, self.O,
-                         self.O, self.k[0], self.KWP, self.s[0], 1 if fold.act == 1 else 0, 0, hip.stream())
-                return
-            hip.call('sn_conv_stem_fwd', self.xp, self.w.w16, bias, dst, self.N, self.Hp, self.Wp, self.Ho, self.Wo, self.O,
-                     self.O, self.k[0], self.KWP, self.s[0], 0, 1 if self.out_f32 else 0, hip.stream())
-            return
-        if self.depthwise:
-            if bias is not None or self.out_f32:
-                raise NotImplementedError('depthwise convolution with bias / fp32 output (%s)' % self.node.name)
-            hip.call('sn_dwconv_fwd', x, self.w.w16, dst, self.N, self.H, self.W, self.C, self.C, self.O, self.k[0], self.k[1],
-                     self.s[0], self.p[0], self.d[0], hip.stream())
-            return
-        res = getattr(self, 'fused_residual', None)
-        if res is not None:      # y = conv(x) + residual written straight into the consuming add's tensor (BinaryStep)
-            dst = self.fused_dst.t
-        if getattr(self, 'stats_buf', None) is not None and self.ex.is_train:
+            self._fwd_stem(dst, bias)
+        elif self.depthwise:
+            self._fwd_depthwise(x, dst, bias)
+        else:
+            self._fwd_igemm(x, dst, bias)
+
+    def _fwd_operands(self, bias):
+        """-> (weights, bias, ReLU flag) of a forward launch: the folded copies when a BatchNorm (+ ReLU) rides in the weights / bias /
+        epilogue (refold) -- frozen conv0 -> bn0 (-> relu0) in training, every BatchNorm that alone reads its convolution at test time"""
+        if self.fold_bn is None:
+            return self.w.w16, bias, 0
+        if self.wf is None:
+            raise RuntimeError('%s: folded BatchNorm weights missing (parameters were never set)' % self.node.name)
+        return self.wf, self.bf, 1 if self.fold_bn.act == 1 else 0
+
+    def _fwd_stem(self, dst, bias):
+        src, scale, shift = (self.x.stem if self.x.stem is not None else (self.x, None, None))
+        hip.call('sn_pack_stem_input', src.t, self.xp, self.N, self.C, self.H, self.W, self.Hp, self.Wp, self.p[0], self.p[1],
+                 scale, shift, hip.stream())
+        w, b, relu = self._fwd_operands(bias)
+        hip.call('sn_conv_stem_fwd', self.xp, w, b, dst, self.N, self.Hp, self.Wp, self.Ho, self.Wo, self.O, self.O, self.k[0],
+                 self.KWP, self.s[0], relu, 1 if self.out_f32 else 0, hip.stream())
+
+    def _fwd_depthwise(self, x, dst, bias):
+        if bias is not None or self.out_f32:
+            raise NotImplementedError('depthwise convolution with bias / fp32 output (%s)' % self.node.name)
+        hip.call('sn_dwconv_fwd', x, self.w.w16, dst, self.N, self.H, self.W, self.C, self.C, self.O, self.k[0], self.k[1],
+                 self.s[0], self.p[0], self.d[0], hip.stream())
+
+    def _fwd_igemm(self, x, dst, bias):
+        ex, geom = self.ex, self.geom()
+        res = None
+        if self.fused_residual is not None:      # y = conv(x) + residual written straight into the consuming add's tensor (BinaryStep)
+            res, dst = self.fused_residual.t, self.fused_dst.t
+        if self.stats_buf is not None and ex.is_train:
             # the consuming BatchNorm's sum / sum of squares come out of the epilogue (no separate read pass)
             if self._stats_blocks() != self.stats_blocks:
                 raise RuntimeError('%s: kernel selection changed after the statistics buffer was sized' % self.node.name)
-            hip.call('sn_conv_fwd_stats', x, self.w.w16, bias, None if res is None else res.t, dst, self.N, self.H, self.W, self.C,
-                     self.C, self.O, self.O, 0 if res is None else self.O, self.k[0], self.k[1], self.s[0], self.p[0], self.d[0], 0,
-                     self.stats_buf, hip.stream())
+            hip.call('sn_conv_fwd_stats', x, self.w.w16, bias, res, dst, *geom, 0, self.stats_buf, hip.stream())
             return
-        fold = getattr(self, 'fold_bn', None)
-        w, b, relu = self.w.w16, bias, 0
-        if fold is not None:     # test-time: the BatchNorm (+ ReLU) reading this output is part of the epilogue (refold)
-            if getattr(self, 'wf', None) is None:
-                raise RuntimeError('%s: folded BatchNorm weights missing (parameters were never set)' % self.node.name)
-            w, b, relu = self.wf, self.bf, 1 if fold.act == 1 else 0
-        geom = (self.N, self.H, self.W, self.C, self.C, self.O, self.O, 0 if res is None else self.O, self.k[0], self.k[1], self.s[0],
-                self.p[0], self.d[0])
+        w, b, relu = self._fwd_operands(bias)
         if not ex.for_training and not self.out_f32:
             # test-time launches with far fewer output tiles than CUs (batches of two FocusChips): contraction split over copies
             # of the tile grid (sn_conv_fwd_splitk; the query is 0 for every layer that would not be split)
-            if getattr(self, '_splitk_bytes', None) is None:
+            if self._splitk_bytes is None:
                 self._splitk_bytes = int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
-            dual = getattr(self, 'dual_bn', None)
+            ws = ex.ws.get(self._splitk_bytes) if self._splitk_bytes else None
+            dual = self.dual_bn
             if dual is not None and not ex.is_train:
                 # the next unit's BatchNorm + ReLU as the epilogue's second output (BatchNormStep.setup), split-K or not
                 if not dual._global_ready:
-                    hip.call('sn_bn_global_scale_shift', None if dual.fix_gamma else dual.gamma.master, dual.beta.master, dual.mean,
-                             dual.var, dual.C, dual.eps, dual.scale, dual.shift, hip.stream())
-                    dual._global_ready = True
-                hip.call('sn_conv_fwd_dual', x, w, b, None if res is None else res.t, dst, *geom, relu, dual.y.t, self.O, dual.scale,
-                         dual.shift, 1 if dual.act == 1 else 0, ex.ws.get(self._splitk_bytes) if self._splitk_bytes else None,
-                         self._splitk_bytes, hip.stream())
+                    dual.fold_global()
+                hip.call('sn_conv_fwd_dual', x, w, b, res, dst, *geom, relu, dual.y.t, self.O, dual.scale, dual.shift,
+                         1 if dual.act == 1 else 0, ws, self._splitk_bytes, hip.stream())
                 return
             if self._splitk_bytes:
-                hip.call('sn_conv_fwd_splitk', x, w, b, None if res is None else res.t, dst, *geom, relu, ex.ws.get(self._splitk_bytes),
-                         self._splitk_bytes, hip.stream())
+                hip.call('sn_conv_fwd_splitk', x, w, b, res, dst, *geom, relu, ws, self._splitk_bytes, hip.stream())
                 return
-        hip.call('sn_conv_fwd', x, w, b, None if res is None else res.t, dst, *geom, relu, 1 if self.out_f32 else 0, hip.stream())
+        hip.call('sn_conv_fwd', x, w, b, res, dst, *geom, relu, 1 if self.out_f32 else 0, hip.stream())
 
     def launch_dgrad(self, dy, Op, acc, dx):
         if self.depthwise:
@@ -621,7 +626,7 @@ class ConvolutionStep(_GemmLike):
             nblk = hip.query('sn_conv_dgrad_bn_blocks', self.N, self.H, self.W, self.C, self.C, Op, Op, 0, self.k[0], self.k[1],
                              self.s[0], self.p[0], self.d[0])
             if nblk > 0:
-                if getattr(self, 'bnb_buf', None) is None or self.bnb_buf.shape[0] != nblk:
+                if self.bnb_buf is None or self.bnb_buf.shape[0] != nblk:
                     self.bnb_buf = self.ex.empty((nblk, 2, self.C), F32)
                 hip.call('sn_conv_dgrad_bn', dy, self.w.wT16, None, dx, self.N, self.H, self.W, self.C, self.C, Op, Op, 0, self.k[0],
                          self.k[1], self.s[0], self.p[0], self.d[0], self.ex.as_act(bn.x), self.C, bn.scale, bn.shift, bn.save_mean,
@@ -639,7 +644,7 @@ class ConvolutionStep(_GemmLike):
         if acc is not None or self.x.fmt != 'act':
             return None
         bn = self.x.producer
-        if type(bn).__name__ != 'BatchNormStep' or bn.sole_consumer is not self.node or bn.global_stats or bn.is_stem:
+        if not isinstance(bn, BatchNormStep) or bn.sole_consumer is not self.node or bn.global_stats or bn.is_stem:
             return None
         if not (self.ex.is_train and bn.y.needs_grad and bn.x.fmt == 'act'):
             return None
@@ -669,12 +674,12 @@ def _fwd_splitk(step, x, w, bias, dst, geom):
     ex = step.ex
     if ex.for_training or ex.is_train:
         return False
-    nbytes = getattr(step, '_splitk_bytes', None)
+    nbytes = step._splitk_bytes
     if nbytes is None:
         nbytes = step._splitk_bytes = int(hip.query('sn_conv_fwd_splitk_workspace_bytes', *geom))
     if not nbytes:
         return False
-    if getattr(step, 'out_f32', False):
+    if step.out_f32:
         N, H, W, C, ips, O, ops_, _rps, KH, KW, st, pad, dil = geom
         hip.call('sn_conv_fwd_splitk_f32', x, w, bias, dst, N, H, W, C, ips, O, ops_, KH, KW, st, pad, dil, 0, ex.ws.get(nbytes), nbytes,
                  hip.stream())
@@ -695,19 +700,16 @@ class FullyConnectedStep(_GemmLike):
         # a 4-D channels-last input is consumed in (h, w, c) order: the weight is permuted once instead
         self.fc_in = (xs[1], xs[2], xs[3]) if len(xs) == 4 and xs[2] * xs[3] > 1 else None
         self.k, self.s, self.p, self.d = (1, 1), (1, 1), (0, 0), (1, 1)
-        self.is_stem = False
+        self.is_stem = self.depthwise = False
 
     def x_tensor(self):
         return self.ex.as_act(self.x)
 
-    def x_shape_nhwc(self):
-        return self.x.nhwc()
-
     def launch_fwd(self, x, dst, bias):
-        if _fwd_splitk(self, x, self.w.w16, bias, dst, (self.N, 1, 1, self.C, self.C, self.O, self.O, 0, 1, 1, 1, 0, 1)):
+        geom = gemm_geom(self.N, self.C, self.O)
+        if _fwd_splitk(self, x, self.w.w16, bias, dst, geom):
             return
-        hip.call('sn_conv_fwd', x, self.w.w16, bias, None, dst, self.N, 1, 1, self.C, self.C, self.O, self.O, 0, 1, 1, 1, 0, 1, 0,
-                 1 if self.out_f32 else 0, hip.stream())
+        hip.call('sn_conv_fwd', x, self.w.w16, bias, None, dst, *geom, 0, 1 if self.out_f32 else 0, hip.stream())
 
     def launch_dgrad(self, dy, Op, acc, dx):
         hip.call('sn_conv_dgrad', dy, self.w.wT16, acc, dx, self.N, 1, 1, self.C, self.C, Op, Op, self.C, 1, 1, 1, 0, 1, 0,
@@ -737,6 +739,9 @@ class DeformableConvolutionStep(Step):
         self.y.needs_grad = ex.for_training
         self.col = ex.act_empty((self.N * self.Ho * self.Wo, self.T * self.C), F16)
         self.wT_flat = None
+        self.out_f32 = False              # (_fwd_splitk: the column GEMM writes fp16)
+        self._splitk_bytes = None         # first test-time forward: scratch bytes of the column GEMM's split-K launch (0: not split)
+        self.dws = None                   # first backward: max |offset| of the launch, prunes the data gradient's scan
 
     def transpose_jobs(self, only_trainable=False):
         """the deformable convolution's data gradient is a 1x1 GEMM over the (tap, channel) column: W^T as [T*C][O]"""
@@ -754,10 +759,10 @@ class DeformableConvolutionStep(Step):
                  self.d[0], self.dg, oc, 0, hip.stream())
         M, K = self.col.shape
         bias = self.b.master if self.b is not None else None
-        if _fwd_splitk(self, self.col, self.w.w16, bias, self.y.t, (M, 1, 1, K, K, self.O, self.O, 0, 1, 1, 1, 0, 1)):
+        geom = gemm_geom(M, K, self.O)
+        if _fwd_splitk(self, self.col, self.w.w16, bias, self.y.t, geom):
             return
-        hip.call('sn_conv_fwd', self.col, self.w.w16, bias, None, self.y.t, M, 1, 1, K, K, self.O, self.O, 0, 1, 1, 1, 0, 1, 0, 0,
-                 hip.stream())
+        hip.call('sn_conv_fwd', self.col, self.w.w16, bias, None, self.y.t, *geom, 0, 0, hip.stream())
 
     def backward(self):
         ex = self.ex
@@ -780,8 +785,8 @@ class DeformableConvolutionStep(Step):
             oc = self.off.shape[1]
             d16 = ex.empty((self.N, self.H, self.W, self.C), F16) if self.x.needs_grad else None
             d_off = ex.empty((self.N, self.Ho, self.Wo, oc), F16) if self.off.needs_grad else None
-            if getattr(self, 'dws', None) is None:
-                self.dws = ex.zeros((16,), torch.uint8)      # max |offset| of the launch: prunes the data gradient's scan
+            if self.dws is None:
+                self.dws = ex.zeros((16,), torch.uint8)
             hip.call('sn_deform_col2im', dcol, ex.as_act(self.x), ex.as_act(self.off), d16, 0, d_off, self.N, self.H, self.W,
                      self.C, self.k[0], self.k[1], self.s[0], self.p[0], self.d[0], self.dg, oc, 0, self.dws, hip.stream())
             if self.x.needs_grad:
@@ -931,8 +936,8 @@ class BinaryStep(Step):
             me, other = (a, b) if order(a) > order(b) else (b, a)
             st = me.producer
             cons = ex.consumers.get((id(st.node), 0), []) if st is not None else []
-            if (type(st).__name__ == 'ConvolutionStep' and not st.depthwise and not st.is_stem and not st.out_f32 and
-                    len(cons) == 1 and getattr(st, 'fused_residual', None) is None and me is not other):
+            if (isinstance(st, ConvolutionStep) and not st.depthwise and not st.is_stem and not st.out_f32 and
+                    len(cons) == 1 and st.fused_residual is None and me is not other):
                 st.fused_residual, st.fused_dst = other, self.y
                 self.fused_conv = st
 
@@ -959,7 +964,7 @@ class BinaryStep(Step):
             if self.lhs.grad is not None and self.lhs.grad is self.rhs.grad:      # one tensor, several owners: see Executor.grad_slot
                 # the owners of ONE gradient tensor share one list.  Nested adds (d = a + e, a = b + c) hand d's tensor to e, b
                 # and c: the inner add extends the list its own output already belongs to (minus that output: consumed here)
-                group = getattr(self.y, 'grad_group', None)
+                group = self.y.grad_group
                 if group is None or self.y.grad is not self.lhs.grad:
                     group = []
                 elif self.y in group:
@@ -1175,43 +1180,39 @@ class MultiProposalStep(_ProposalBase):
 
 @register('MultiProposalTarget')
 class MultiProposalTargetStep(_ProposalBase):
+    n_outs = 4          # rois, label, bbox_target, bbox_weight
+
     def setup(self):
         self.common()
         self.gt, self.vr = self.data_in('gt_boxes'), self.data_in('valid_ranges')
         self.G = self.gt.shape[1]
         self.fg = float(self.a.get('fg_thresh', 0.5))
         self.stds = np.array(self.a.get('bbox_stds', (0.1, 0.1, 0.2, 0.2)), np.float32)
-        self.outs = [self.new_out('f32', i) for i in range(4)]
+        self.outs = [self.new_out('f32', i) for i in range(self.n_outs)]
+
+    def target_args(self):
+        """what sn_multi_proposal_target and sn_multi_proposal_target_mask take alike: inputs, anchors, geometry, thresholds, scratch"""
+        ex = self.ex
+        return (ex.as_f32(self.cls), ex.as_f32(self.bbox), ex.as_f32(self.info), ex.as_f32(self.gt), ex.as_f32(self.vr), self.base,
+                self.B, self.A, self.Fh, self.Fw, self.stride, self.G, self.pre, self.post, self.thresh, self.min_size, self.fg,
+                self.stds.ctypes.data, self.wsbuf)
 
     def forward(self):
-        ex = self.ex
-        rois, label, tgt, wgt = [o.t for o in self.outs]
-        hip.call('sn_multi_proposal_target', ex.as_f32(self.cls), ex.as_f32(self.bbox), ex.as_f32(self.info), ex.as_f32(self.gt),
-                 ex.as_f32(self.vr), self.base, self.B, self.A, self.Fh, self.Fw, self.stride, self.G, self.pre, self.post, self.thresh,
-                 self.min_size, self.fg, self.stds.ctypes.data, self.wsbuf, rois, label, tgt, wgt, hip.stream())
+        hip.call('sn_multi_proposal_target', *self.target_args(), *[o.t for o in self.outs], hip.stream())
 
 
 @register('MultiProposalTargetMask')
-class MultiProposalTargetMaskStep(_ProposalBase):
+class MultiProposalTargetMaskStep(MultiProposalTargetStep):
     """resnet_mx_101_e2e_mask.py:317-318: MultiProposalTarget + the mask RoIs of every chip and the GT row each matched."""
+    n_outs = 6          # ... + mask rois, mask ids
 
     def setup(self):
-        self.common()
-        self.gt, self.vr = self.data_in('gt_boxes'), self.data_in('valid_ranges')
-        self.G = self.gt.shape[1]
-        self.fg = float(self.a.get('fg_thresh', 0.5))
-        self.stds = np.array(self.a.get('bbox_stds', (0.1, 0.1, 0.2, 0.2)), np.float32)
-        self.outs = [self.new_out('f32', i) for i in range(6)]
+        MultiProposalTargetStep.setup(self)
         self.nm = self.outs[4].shape[0] // self.B
         self.match = self.ex.empty((self.B * self.post,), F32)
 
     def forward(self):
-        ex = self.ex
-        rois, label, tgt, wgt, mrois, mids = [o.t for o in self.outs]
-        hip.call('sn_multi_proposal_target_mask', ex.as_f32(self.cls), ex.as_f32(self.bbox), ex.as_f32(self.info), ex.as_f32(self.gt),
-                 ex.as_f32(self.vr), self.base, self.B, self.A, self.Fh, self.Fw, self.stride, self.G, self.pre, self.post, self.thresh,
-                 self.min_size, self.fg, self.stds.ctypes.data, self.wsbuf, self.match, self.nm, rois, label, tgt, wgt, mrois, mids,
-                 hip.stream())
+        hip.call('sn_multi_proposal_target_mask', *self.target_args(), self.match, self.nm, *[o.t for o in self.outs], hip.stream())
 
 
 @register('MaskRcnnTarget')
@@ -1273,11 +1274,10 @@ class DeconvolutionStep(Step):
             ex.on_side(lambda: _wgrad(ex, dtmp, x, self.w.grad, self.N, self.H, self.W, self.C, self.C, O4, O4, 1, 1, 1, 0, 1),
                        keep=(dtmp, x))
         if self.x.needs_grad:
-            dx, acc = ex.grad_slot(self.x) if self.x.fmt == 'act' else (ex.empty((self.N, self.H, self.W, self.C), F16), None)
+            dx, acc = ex.input_grad_dst(self.x)
             hip.call('sn_conv_dgrad', dtmp, self.w.wT16, acc, dx, self.N, self.H, self.W, self.C, self.C, O4, O4, self.C,
                      1, 1, 1, 0, 1, 0, hip.stream())
-            if self.x.fmt != 'act':
-                ex.add_grad(self.x, dx, 'act')
+            ex.input_grad_done(self.x, dx)
         self.y.grad = None
 
 
@@ -1340,8 +1340,8 @@ class DPSROIPoolStep(Step):
         # (Param.out_perm; reference order at the checkpoint boundary as ever) -- and the pooling kernels index (gh*G + gw)*D + d.
         self.gm = 0
         prod = self.x.producer
-        if (self.G > 1 and type(prod).__name__ == 'ConvolutionStep'
-                and self.x.fmt == 'act' and not prod.depthwise and not prod.out_f32 and getattr(prod, 'fold_bn', None) is None
+        if (self.G > 1 and isinstance(prod, ConvolutionStep)
+                and self.x.fmt == 'act' and not prod.depthwise and not prod.out_f32 and prod.fold_bn is None
                 and len(ex.consumers.get((id(prod.node), 0), [])) == 1 and (id(prod.node), 0) not in ex.head_keys):
             G, D = self.G, self.D
             perm = np.empty(D * G * G, np.int64)
