@@ -358,6 +358,22 @@ int sn_dwconv_dgrad(const void *dy, const void *w, const void *accumulate, void 
 size_t sn_dwconv_wgrad_workspace_bytes(int N, int H, int W, int C, int KH, int KW, int stride, int pad, int dil);
 int sn_dwconv_wgrad(const void *dy, const void *x, float *dw, int N, int H, int W, int C, int dy_pix_stride, int x_pix_stride,
                     int KH, int KW, int stride, int pad, int dil, void *ws, size_t ws_bytes, sn_stream_t stream);
+/* Grouped convolution (Convolution with 1 < num_group < channels; the ResNeXt 3x3 with num_group = 64), channels-last fp16
+ * with pixel pitches, fp32 accumulation.  Weights are the compact [O][KH*KW][C/groups] fp16 layout for the forward pass AND the
+ * data gradient (no transposed copy).  Cg == Og in {4, 8, 16, 32} with C % 32 == 0, a 1x1 or 3x3 kernel and stride 1 or 2 run on
+ * the matrix cores; every other shape with C % groups == O % groups == 0 takes a plain kernel.  groups == 1 (sn_conv_*) and
+ * groups == C == O (sn_dwconv_*) are argument errors.  fwd: bias fp32 [O] or NULL, optional ReLU; out_f32 writes fp32 with the
+ * same pitch (plain kernel).  dgrad adds `accumulate` (may be NULL / alias dx).  wgrad accumulates (+=) into fp32
+ * dw [O][KH*KW][C/groups] through per-block partials in `ws` summed in block order (deterministic, no atomics). */
+int sn_gconv_fwd(const void *x, const void *w, const float *bias, void *y, int N, int H, int W, int C, int in_pix_stride, int O,
+                 int out_pix_stride, int groups, int KH, int KW, int stride, int pad, int dil, int relu, int out_f32,
+                 sn_stream_t stream);
+int sn_gconv_dgrad(const void *dy, const void *w, const void *accumulate, void *dx, int N, int H, int W, int C, int O,
+                   int dy_pix_stride, int acc_pix_stride, int dx_pix_stride, int groups, int KH, int KW, int stride, int pad, int dil,
+                   sn_stream_t stream);
+size_t sn_gconv_wgrad_workspace_bytes(int N, int H, int W, int C, int O, int groups, int KH, int KW, int stride, int pad, int dil);
+int sn_gconv_wgrad(const void *dy, const void *x, float *dw, int N, int H, int W, int C, int O, int dy_pix_stride, int x_pix_stride,
+                   int groups, int KH, int KW, int stride, int pad, int dil, void *ws, size_t ws_bytes, sn_stream_t stream);
 /* clip(lo, hi) (mx.sym.clip; relu6) forward, or backward = (lo <= ref <= hi ? a : 0) [+ accumulate]. */
 int sn_clip_f16(const void *a, const void *ref, const void *accumulate, void *y, long rows, int C, int ps_a, int ps_ref, int ps_acc,
                 int ps_y, float lo, float hi, int backward, sn_stream_t stream);

@@ -89,6 +89,14 @@ def res101_e2e_mask(batch_images=20):
     return c
 
 
+def resnext101_e2e(batch_images=20):
+    """The R101 recipe on the ResNeXt-101 64x4d trunk (symbols/faster/resnext_mx_101_e2e.py; the reference ships the trunk,
+    symbols/faster/resnext_mx_101.py, and no config for it)."""
+    c = res101_e2e(batch_images)
+    c.symbol = 'resnext_mx_101_e2e'
+    return c
+
+
 def res101_e2e_autofocus(batch_images=20):
     """configs/faster/sniper_res101_e2e_autofocus.yml TEST section (BASELINE C5): coarse-to-fine scales, FocusChips."""
     c = res101_e2e(batch_images)

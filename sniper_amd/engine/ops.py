@@ -413,7 +413,7 @@ class _GemmLike(Step):
         self.y = self.new_out('f32' if self.out_f32 else 'act')
         wt = ex.for_training and (self.pname('weight') not in ex.fixed)
         self.y.needs_grad = ex.for_training and (self.x.needs_grad or wt)
-        if self.x.needs_grad and ex.for_training and not self.depthwise:
+        if self.x.needs_grad and ex.for_training and self.groups == 1:     # (depthwise / grouped data gradients read the compact w)
             self.w.need_wT = True
         self.tmp_nhwc32 = None
         if self.out_f32 and self.Ho * self.Wo > 1:
@@ -501,10 +501,13 @@ class ConvolutionStep(_GemmLike):
         self.N, self.C, self.H, self.W = self.x.shape
         _, self.O, self.Ho, self.Wo = self.out_shape()
         g = int(a.get('num_group', 1))
-        self.depthwise = g > 1
-        if self.depthwise and not (g == self.C == self.O):
-            raise NotImplementedError('grouped convolution with num_group=%d, %d -> %d channels (%s): only depthwise '
-                                      '(num_group == channels, MobileNetV2) is built' % (g, self.C, self.O, self.node.name))
+        if g < 1 or self.C % g or self.O % g:
+            raise ValueError('%s: num_group=%d does not divide %d -> %d channels' % (self.node.name, g, self.C, self.O))
+        # groups == 1: the implicit-GEMM kernels and every fusion below; depthwise (groups == C == O, MobileNetV2): dwconv.hip;
+        # grouped (anything between, ResNeXt): gconv.hip.  Neither of the last two carries a dense-only fusion.
+        self.groups = g
+        self.depthwise = g > 1 and g == self.C == self.O
+        self.grouped = g > 1 and not self.depthwise
         self.wkind, self.fc_in = 'conv', None
         self.is_stem = self.C <= 4
         if self.is_stem:
@@ -529,7 +532,7 @@ class ConvolutionStep(_GemmLike):
                 self.k[1], self.s[0], self.p[0], self.d[0])
 
     def _stats_blocks(self):
-        if self.is_stem or self.depthwise or self.out_f32:
+        if self.is_stem or self.groups > 1 or self.out_f32:
             return 0
         return hip.query('sn_conv_fwd_stats_blocks', *self.geom())
 
@@ -546,7 +549,7 @@ class ConvolutionStep(_GemmLike):
     def request_dual(self, bn):
         """A test-time moving-statistics BatchNorm (+ ReLU) that reads this convolution's output -- or the residual sum its
         epilogue writes -- and cannot fold into it asks to be written as the epilogue's second output.  -> accepted?"""
-        if (self.dual_bn is not None or self.fold_bn is not None or self.is_stem or self.depthwise or self.out_f32 or
+        if (self.dual_bn is not None or self.fold_bn is not None or self.is_stem or self.groups > 1 or self.out_f32 or
                 self.ex.for_training):
             return False
         if not hip.query('sn_conv_fwd_dual_ok', *self.geom(), self.O):
@@ -559,6 +562,10 @@ class ConvolutionStep(_GemmLike):
             self._fwd_stem(dst, bias)
         elif self.depthwise:
             self._fwd_depthwise(x, dst, bias)
+        elif self.grouped:
+            w, b, relu = self._fwd_operands(bias)      # (a folded BatchNorm scales the compact weights row by row like dense ones)
+            hip.call('sn_gconv_fwd', x, w, b, dst, self.N, self.H, self.W, self.C, self.C, self.O, self.O, self.groups,
+                     self.k[0], self.k[1], self.s[0], self.p[0], self.d[0], relu, 1 if self.out_f32 else 0, hip.stream())
         else:
             self._fwd_igemm(x, dst, bias)
 
@@ -621,6 +628,10 @@ class ConvolutionStep(_GemmLike):
             hip.call('sn_dwconv_dgrad', dy, self.w.w16, acc, dx, self.N, self.H, self.W, self.C, Op, self.C, self.C, self.k[0],
                      self.k[1], self.s[0], self.p[0], self.d[0], hip.stream())
             return
+        if self.grouped:
+            hip.call('sn_gconv_dgrad', dy, self.w.w16, acc, dx, self.N, self.H, self.W, self.C, self.O, Op, self.C, self.C,
+                     self.groups, self.k[0], self.k[1], self.s[0], self.p[0], self.d[0], hip.stream())
+            return
         bn = self._bn_below(acc)
         if bn is not None:
             nblk = hip.query('sn_conv_dgrad_bn_blocks', self.N, self.H, self.W, self.C, self.C, Op, Op, 0, self.k[0], self.k[1],
@@ -663,6 +674,12 @@ class ConvolutionStep(_GemmLike):
             hip.call('sn_dwconv_wgrad', dy, x, self.w.grad, self.N, self.H, self.W, self.C, Op, self.C, self.k[0], self.k[1],
                      self.s[0], self.p[0], self.d[0], self.ex.ws.get(need), need, hip.stream())
             return
+        if self.grouped:        # per layer through the shared scratch, like the depthwise one: not a row of the batched tables
+            need = hip.query('sn_gconv_wgrad_workspace_bytes', self.N, self.H, self.W, self.C, self.O, self.groups, self.k[0],
+                             self.k[1], self.s[0], self.p[0], self.d[0])
+            hip.call('sn_gconv_wgrad', dy, x, self.w.grad, self.N, self.H, self.W, self.C, self.O, Op, self.C, self.groups, self.k[0],
+                     self.k[1], self.s[0], self.p[0], self.d[0], self.ex.ws.get(need), need, hip.stream())
+            return
         _wgrad(self.ex, dy, x, self.w.grad, self.N, self.H, self.W, self.C, self.C, self.O, Op, self.k[0], self.k[1],
                self.s[0], self.p[0], self.d[0])
 
@@ -700,7 +717,8 @@ class FullyConnectedStep(_GemmLike):
         # a 4-D channels-last input is consumed in (h, w, c) order: the weight is permuted once instead
         self.fc_in = (xs[1], xs[2], xs[3]) if len(xs) == 4 and xs[2] * xs[3] > 1 else None
         self.k, self.s, self.p, self.d = (1, 1), (1, 1), (0, 0), (1, 1)
-        self.is_stem = self.depthwise = False
+        self.is_stem = self.depthwise = self.grouped = False
+        self.groups = 1
 
     def x_tensor(self):
         return self.ex.as_act(self.x)
@@ -730,6 +748,9 @@ class DeformableConvolutionStep(Step):
         self.k, self.s = _tup(a['kernel']), _tup(a.get('stride', (1, 1)))
         self.p, self.d = _tup(a.get('pad', (0, 0))), _tup(a.get('dilate', (1, 1)))
         self.dg = int(a.get('num_deformable_group', 1))
+        if int(a.get('num_group', 1)) > 1:
+            raise NotImplementedError('%s: DeformableConvolution with num_group=%s (grouped deformable convolution is not built)' %
+                                      (self.node.name, a.get('num_group')))
         self.N, self.C, self.H, self.W = self.x.shape
         _, self.O, self.Ho, self.Wo = self.out_shape()
         self.T = self.k[0] * self.k[1]
@@ -936,7 +957,7 @@ class BinaryStep(Step):
             me, other = (a, b) if order(a) > order(b) else (b, a)
             st = me.producer
             cons = ex.consumers.get((id(st.node), 0), []) if st is not None else []
-            if (isinstance(st, ConvolutionStep) and not st.depthwise and not st.is_stem and not st.out_f32 and
+            if (isinstance(st, ConvolutionStep) and st.groups == 1 and not st.is_stem and not st.out_f32 and
                     len(cons) == 1 and st.fused_residual is None and me is not other):
                 st.fused_residual, st.fused_dst = other, self.y
                 self.fused_conv = st
@@ -1341,7 +1362,7 @@ class DPSROIPoolStep(Step):
         self.gm = 0
         prod = self.x.producer
         if (self.G > 1 and isinstance(prod, ConvolutionStep)
-                and self.x.fmt == 'act' and not prod.depthwise and not prod.out_f32 and prod.fold_bn is None
+                and self.x.fmt == 'act' and prod.groups == 1 and not prod.out_f32 and prod.fold_bn is None
                 and len(ex.consumers.get((id(prod.node), 0), [])) == 1 and (id(prod.node), 0) not in ex.head_keys):
             G, D = self.G, self.D
             perm = np.empty(D * G * G, np.int64)
