@@ -384,6 +384,19 @@ int sn_ew_f16(const void *a, const void *b, const void *ref, void *y, long rows,
 /* fp32 element-wise: op 0 a-b, 1 a+b, 2 a*b, 3 a*scalar, 4 fill(scalar). */
 int sn_ew_f32(const float *a, const float *b, float *out, long n, int op, float scalar, sn_stream_t stream);
 int sn_maxpool_fwd(const void *x, void *y, int N, int H, int W, int C, int k, int stride, int pad, sn_stream_t stream);
+/* Gradient of sn_maxpool_fwd, channels-last fp16: x (N,H,W,C) the pool's input, dy (N,Ho,Wo,C), dx (N,H,W,C).  The pooled output
+ * is not an argument: the decision is re-derived from x.
+ *  - Window order: a window is scanned row-major over its valid positions; padding is never a candidate.
+ *  - Tie rule: the window's whole dy goes to the FIRST position in that order whose value equals the window maximum (torch's
+ *    CPU rule): p wins w iff x[p] > every earlier valid element of w and x[p] >= every later one.  Unlike torch, a NaN never
+ *    wins a window (sn_maxpool_fwd's fmaxf skips it too); a window of NaNs alone goes to its first valid position.
+ *  - Arithmetic: dx[p] = fp16(sum of float(dy[w]) over the windows p wins (+ float(accumulate[p]))), summed in fp32, rounded once.
+ *  - Ownership: a gather.  Every dx element is written exactly once by exactly one thread: no atomics, no zero fill before it,
+ *    bitwise reproducible.  accumulate: NULL, or fp16 of dx's geometry, may alias dx.
+ *  - Accepted: C % 8 == 0, 1 <= stride <= k <= 7, 0 <= pad <= k / 2 (torch's own limit), the window within the padded input;
+ *    anything else, or a NULL dy / x / dx, is SN_ERR_ARG before any launch.  3x3 / stride 2 / pad 1 has a kernel of its own. */
+int sn_maxpool_bwd(const void *dy, const void *x, const void *accumulate, void *dx, int N, int H, int W, int C, int k, int stride,
+                   int pad, sn_stream_t stream);
 /* Pooling(pool_type='avg', global_pool=True) over a channels-last fp16 tensor x (N, HW, C) -> y (N, C) fp32 (the R-FCN
  * vote over the position-sensitive bins, BASELINE config C4), and its gradient dx = dy / HW (fp16, overwritten). */
 int sn_avgpool_global_fwd(const void *x, float *y, int N, int HW, int C, sn_stream_t stream);

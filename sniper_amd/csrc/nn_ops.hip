@@ -738,8 +738,8 @@ SN_EXPORT int sn_ew_f16(const void *a, const void *b, const void *ref, void *y, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Max pooling, channels-last fp16 (resnet_mx_101_e2e.py:409: 3x3 stride 2 pad 1).  Forward only:
-// the stem is frozen (network.FIXED_PARAMS), nothing upstream needs a gradient.
+// Max pooling, channels-last fp16 (resnet_mx_101_e2e.py:409: 3x3 stride 2 pad 1).  The backward pass (below the forward one)
+// runs only when something upstream trains: network.FIXED_PARAMS without conv0 / bn0 / stage1.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void maxpool_kernel(const half_t *__restrict__ x, half_t *__restrict__ y, int N, int H,
                                                       int W, int C, int Ho, int Wo, int k, int stride, int pad) {
@@ -778,6 +778,221 @@ SN_EXPORT int sn_maxpool_fwd(const void *x, void *y, int N, int H, int W, int C,
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
   hipLaunchKernelGGL(maxpool_kernel, dim3(ew_blocks((long)N * Ho * Wo * (C / 8))), dim3(256), 0, sn_stream(stream),
                      (const half_t *)x, (half_t *)y, N, H, W, C, Ho, Wo, k, stride, pad);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
+// Max pooling backward: dx[p] = fp16(sum of dy[w] over the windows w that p wins [+ accumulate[p]]), a gather -- every dx element is
+// written once by one thread, no atomics, no fill.  The winner of a window is re-derived from x: scanned row-major over the valid
+// positions, the first one takes the window, a later one only if its value is greater -- torch's CPU rule, so of several equal
+// maxima the FIRST wins.  (A NaN never wins: the forward's fmaxf skips it too.)
+//
+// 3x3 / stride 2 / pad 1 (the only shape the networks launch): a block owns a tile of 32 x 32 input pixels x 64 channels.  Pass 1
+// decides the 17 x 17 windows that touch the tile, one lane per window and 8 channels (nine 16-byte loads of x, batched), and leaves
+// the winning tap of each channel as a 4-bit code in LDS: 17 * 17 * 8 lanes * 4 bytes = 9248 bytes.  Pass 2 walks the tile in 2 x 2
+// pixel quads: the quad (2a.., 2b..) lies in the windows (a, b), (a, b+1), (a+1, b), (a+1, b+1) and in no other, at fixed taps, so a
+// lane reads four codes and four dy vectors and writes four dx vectors.  x is read from global memory (not staged in LDS): a block
+// asks for its tile plus a one-pixel halo, 34^2 / 32^2 of the tile.  Measured: DESIGN.md section 14, profiles/full_trunk_step.txt.
+constexpr int kPoolQ = 16;              // quads per tile side
+constexpr int kPoolWin = kPoolQ + 1;    // windows per tile side
+
+__device__ __forceinline__ void pool_take(const half8 &d, unsigned code, unsigned tap, float *s) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s[j] += ((code >> (4 * j)) & 15u) == tap ? (float)d[j] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const half_t *__restrict__ dy, const half_t *__restrict__ x,
+                                                          const half_t *acc, half_t *dx, int H, int W, int C, int Ho, int Wo,
+                                                          int tiles_y, int tiles_x, int chunks) {
+  __shared__ unsigned win[kPoolWin * kPoolWin * 8];
+  int b = blockIdx.x;
+  const int chunk = b % chunks; b /= chunks;
+  const int tx = b % tiles_x; b /= tiles_x;
+  const int ty = b % tiles_y;
+  const int n = b / tiles_y;
+  const int cpr = C >> 3;
+  const int l = threadIdx.x & 7;
+  const bool lane_on = chunk * 8 + l < cpr;
+  const int ch = (chunk * 8 + l) * 8;
+  const half_t *xn = x + (size_t)n * H * W * C + ch;
+  const half_t *dyn = dy + (size_t)n * Ho * Wo * C + ch;
+  const size_t img = (size_t)n * H * W * C + ch;
+
+#pragma unroll 1
+  for (int i = threadIdx.x; i < kPoolWin * kPoolWin * 8; i += 256) {
+    const int wx = (i >> 3) % kPoolWin, wy = (i >> 3) / kPoolWin;
+    const int oy = ty * kPoolQ + wy, ox = tx * kPoolQ + wx;
+    if (!lane_on || oy >= Ho || ox >= Wo) continue;
+    const half_t ninf = (half_t)-__builtin_inff(), nan = (half_t)__builtin_nanf("");
+    const half8 out = {nan, nan, nan, nan, nan, nan, nan, nan};                // padding: equals nothing, and the maximum skips it
+    half8 v[9];
+    half8 m = {ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int sy = 2 * oy - 1 + t / 3, sx = 2 * ox - 1 + t % 3;
+      const bool ok = (unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W;
+      const int cy = min(max(sy, 0), H - 1), cx = min(max(sx, 0), W - 1);      // (a clamped address: the load is unconditional)
+      v[t] = *reinterpret_cast<const half8 *>(xn + ((size_t)cy * W + cx) * C);
+      v[t] = ok ? v[t] : out;
+      m = __builtin_elementwise_max(m, v[t]);                                  // (packed; skips NaNs like the forward's fmaxf)
+    }
+    // the winner is the first valid tap that equals the maximum; a window of NaNs alone goes to its first valid tap
+    unsigned tap[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tap[j] = (oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0);
+#pragma unroll
+    for (int t = 8; t >= 0; --t) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tap[j] = v[t][j] == m[j] ? t : tap[j];
+    }
+    unsigned code = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) code |= tap[j] << (4 * j);
+    win[i] = code;
+  }
+  __syncthreads();
+
+#pragma unroll 1
+  for (int q = threadIdx.x; q < kPoolQ * kPoolQ * 8; q += 256) {
+    const int qx = (q >> 3) % kPoolQ, qy = (q >> 3) / kPoolQ;
+    const int a = ty * kPoolQ + qy, c = tx * kPoolQ + qx;
+    const int py = 2 * a, px = 2 * c;
+    if (!lane_on || py >= H || px >= W) continue;
+    // (py < H gives a < Ho, px < W gives c < Wo: the quad's own window always exists)
+    const bool down = a + 1 < Ho, right = c + 1 < Wo;
+    const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    const unsigned none = 0xffffffffu;       // tap 15: nothing matches
+    const int w00 = (qy * kPoolWin + qx) * 8 + l;
+    const unsigned c00 = win[w00];
+    const unsigned c01 = right ? win[w00 + 8] : none;
+    const unsigned c10 = down ? win[w00 + kPoolWin * 8] : none;
+    const unsigned c11 = down && right ? win[w00 + kPoolWin * 8 + 8] : none;
+    const half_t *d = dyn + ((size_t)a * Wo + c) * C;
+    const half8 d00 = *reinterpret_cast<const half8 *>(d);
+    const half8 d01 = right ? *reinterpret_cast<const half8 *>(d + C) : zero;
+    const half8 d10 = down ? *reinterpret_cast<const half8 *>(d + (size_t)Wo * C) : zero;
+    const half8 d11 = down && right ? *reinterpret_cast<const half8 *>(d + (size_t)Wo * C + C) : zero;
+    const bool has_x = px + 1 < W, has_y = py + 1 < H;
+    const size_t o00 = img + ((size_t)py * W + px) * C, o01 = o00 + C, o10 = o00 + (size_t)W * C, o11 = o10 + C;
+    float s00[8], s01[8], s10[8], s11[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s00[j] = s01[j] = s10[j] = s11[j] = 0.f;
+    if (acc) {
+      const half8 a00 = *reinterpret_cast<const half8 *>(acc + o00);
+      const half8 a01 = has_x ? *reinterpret_cast<const half8 *>(acc + o01) : zero;
+      const half8 a10 = has_y ? *reinterpret_cast<const half8 *>(acc + o10) : zero;
+      const half8 a11 = has_x && has_y ? *reinterpret_cast<const half8 *>(acc + o11) : zero;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s00[j] = (float)a00[j];
+        s01[j] = (float)a01[j];
+        s10[j] = (float)a10[j];
+        s11[j] = (float)a11[j];
+      }
+    }
+    // taps (ky * 3 + kx) of the quad's pixels in its four windows
+    pool_take(d00, c00, 4, s00);
+    pool_take(d00, c00, 5, s01);
+    pool_take(d01, c01, 3, s01);
+    pool_take(d00, c00, 7, s10);
+    pool_take(d10, c10, 1, s10);
+    pool_take(d00, c00, 8, s11);
+    pool_take(d01, c01, 6, s11);
+    pool_take(d10, c10, 2, s11);
+    pool_take(d11, c11, 0, s11);
+    half8 r00, r01, r10, r11;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      r00[j] = (half_t)s00[j];
+      r01[j] = (half_t)s01[j];
+      r10[j] = (half_t)s10[j];
+      r11[j] = (half_t)s11[j];
+    }
+    *reinterpret_cast<half8 *>(dx + o00) = r00;
+    if (has_x) *reinterpret_cast<half8 *>(dx + o01) = r01;
+    if (has_y) *reinterpret_cast<half8 *>(dx + o10) = r10;
+    if (has_x && has_y) *reinterpret_cast<half8 *>(dx + o11) = r11;
+  }
+}
+
+// every other accepted geometry: one lane per input pixel and 8 channels scans each window that covers the pixel
+__global__ __launch_bounds__(256) void maxpool_bwd_plain_kernel(const half_t *__restrict__ dy, const half_t *__restrict__ x,
+                                                                const half_t *acc, half_t *dx, int N, int H, int W, int C, int Ho,
+                                                                int Wo, int k, int stride, int pad) {
+  const int cpr = C >> 3;
+  const long total = (long)N * H * W * cpr;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cpr) * 8;
+    long t = i / cpr;
+    const int px = (int)(t % W); t /= W;
+    const int py = (int)(t % H);
+    const int n = (int)(t / H);
+    float s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = 0.f;
+    if (acc) {
+      const half8 a = *reinterpret_cast<const half8 *>(acc + i * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s[j] = (float)a[j];
+    }
+    const int ty = py + pad - k + 1, tx = px + pad - k + 1;
+    const int oy_lo = ty > 0 ? (ty + stride - 1) / stride : 0, oy_hi = min(Ho - 1, (py + pad) / stride);
+    const int ox_lo = tx > 0 ? (tx + stride - 1) / stride : 0, ox_hi = min(Wo - 1, (px + pad) / stride);
+    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+        // the winner is the first valid position that equals the maximum (NaNs skipped, as the forward's fmaxf does); a window
+        // of NaNs alone goes to its first valid position
+        const int y0 = oy * stride - pad, x0 = ox * stride - pad;
+        half_t m[8];
+        int at[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          m[j] = (half_t)-__builtin_inff();
+          at[j] = max(y0, 0) * W + max(x0, 0);
+        }
+        for (int sy = max(y0, 0); sy < min(y0 + k, H); ++sy) {
+          for (int sx = max(x0, 0); sx < min(x0 + k, W); ++sx) {
+            const half8 v = *reinterpret_cast<const half8 *>(x + (((long)n * H + sy) * W + sx) * C + ch);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const bool take = v[j] > m[j];        // (strictly greater: of equal values the first keeps the window)
+              m[j] = take ? v[j] : m[j];
+              at[j] = take ? sy * W + sx : at[j];
+            }
+          }
+        }
+        const half8 d = *reinterpret_cast<const half8 *>(dy + (((long)n * Ho + oy) * Wo + ox) * C + ch);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] += at[j] == py * W + px ? (float)d[j] : 0.f;
+      }
+    }
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)s[j];
+    *reinterpret_cast<half8 *>(dx + i * 8) = o;
+  }
+}
+
+SN_EXPORT int sn_maxpool_bwd(const void *dy, const void *x, const void *accumulate, void *dx, int N, int H, int W, int C, int k,
+                             int stride, int pad, sn_stream_t stream) {
+  SN_REQUIRE(dy && x && dx, "sn_maxpool_bwd: null pointer (dy, x and dx are required)");
+  SN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "sn_maxpool_bwd: N, H, W > 0 and C a positive multiple of 8 (C = %d)", C);
+  SN_REQUIRE(k >= 1 && k <= 7 && stride >= 1 && stride <= k && pad >= 0 && pad <= k / 2,
+             "sn_maxpool_bwd: needs 1 <= stride <= k <= 7 and 0 <= pad <= k / 2 (k = %d, stride = %d, pad = %d)", k, stride, pad);
+  SN_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k && (long)H * W <= 0x7fffffffL,
+             "sn_maxpool_bwd: the window does not fit the padded input, or H * W >= 2^31");
+  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  if (k == 3 && stride == 2 && pad == 1) {
+    const int tiles_y = sn_div_up(H, 2 * kPoolQ), tiles_x = sn_div_up(W, 2 * kPoolQ), chunks = sn_div_up(C / 8, 8);
+    const long blocks = (long)N * tiles_y * tiles_x * chunks;
+    SN_REQUIRE(blocks <= 0x7fffffffL, "sn_maxpool_bwd: tensor too large for one launch");
+    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, sn_stream(stream), (const half_t *)dy,
+                       (const half_t *)x, (const half_t *)accumulate, (half_t *)dx, H, W, C, Ho, Wo, tiles_y, tiles_x, chunks);
+  } else {
+    hipLaunchKernelGGL(maxpool_bwd_plain_kernel, dim3(ew_blocks((long)N * H * W * (C / 8))), dim3(256), 0, sn_stream(stream),
+                       (const half_t *)dy, (const half_t *)x, (const half_t *)accumulate, (half_t *)dx, N, H, W, C, Ho, Wo, k, stride,
+                       pad);
+  }
   SN_CHECK_LAUNCH();
   return SN_OK;
 }

@@ -839,6 +839,13 @@ class PoolingStep(Step):
         if self.kind != 'max' or self.glob:
             raise NotImplementedError('Pooling %s (%s)' % (a.get('pool_type'), self.node.name))
         self.k, self.s, self.p = _tup(a['kernel']), _tup(a.get('stride', (1, 1))), _tup(a.get('pad', (0, 0)))
+        k, s, p = self.k[0], self.s[0], self.p[0]
+        if self.x.needs_grad and not (self.k == (k, k) and self.s == (s, s) and self.p == (p, p)
+                                      and 1 <= s <= k <= 7 and 0 <= p <= k // 2):
+            # sn_maxpool_bwd's geometry: refused here, at lowering, not at the first backward
+            raise NotImplementedError('Pooling %s: the max-pool backward takes a square window with 1 <= stride <= kernel <= 7 and '
+                                      'pad <= kernel / 2 (kernel %s, stride %s, pad %s), and something below this pool trains'
+                                      % (self.node.name, self.k, self.s, self.p))
         self.y = self.new_out('act')
         self.y.needs_grad = self.x.needs_grad
 
@@ -852,9 +859,16 @@ class PoolingStep(Step):
     def backward(self):
         if self.y.grad is None or not self.x.needs_grad:
             return
-        if self.kind != 'gavg':
-            raise NotImplementedError('max-pool backward (the stem is frozen in every SNIPER config)')
         n, h, w, c = self.x.nhwc()
+        if self.kind != 'gavg':
+            # reached only when something below the pool trains (network.FIXED_PARAMS without conv0 / bn0): the decision is
+            # re-derived from the pool's input, which a training executor keeps (its activations are never recycled)
+            dx, acc = self.ex.input_grad_dst(self.x)
+            hip.call('sn_maxpool_bwd', self.y.grad, self.ex.as_act(self.x), acc, dx, n, h, w, c, self.k[0], self.s[0], self.p[0],
+                     hip.stream())
+            self.ex.input_grad_done(self.x, dx)
+            self.y.grad = None
+            return
         dx = self.ex.empty((n, h, w, c), F16)
         hip.call('sn_avgpool_global_bwd', self.y.grad, dx, n, h * w, c, hip.stream())
         self.ex.add_grad(self.x, dx, 'act')

@@ -33,12 +33,17 @@ class Trainer(object):
     every BatchNorm of the trainable stages normalises with its moving statistics (use_global_stats) and still trains its
     gamma / beta unless network.FIXED_PARAMS names them; MobileNetV2 ignores the flag.  fix_bn is a fine-tuning mode: from the random
     initialisation of a synthetic run the config's own learning rate leaves the frozen statistics behind within a few updates
-    (tests and tools/fix_bn_step.py train such a run at <= 2e-5)."""
+    (tests and tools/fix_bn_step.py train such a run at <= 2e-5).
+    `fixed_params` replaces network.FIXED_PARAMS (None keeps the config's list): [] trains everything -- conv0, bn0 and stage 1
+    included, through the max-pool backward -- except bn_data, which stays folded into the image packing whatever the list says
+    (MXNet would train bn_data_beta; that needs the stem's data gradient, which is never computed here)."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
-                 fix_bn=False):
+                 fix_bn=False, fixed_params=None):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
+        if fixed_params is not None:
+            cfg.network.FIXED_PARAMS = list(fixed_params)
         cfg.TRAIN.USE_NEG_CHIPS = n_proposals > 0
         np.random.seed(seed)
         self.roidb = make_roidb(n_images, seed=seed, n_proposals=n_proposals, with_masks=bool(cfg.TRAIN.WITH_MASK))

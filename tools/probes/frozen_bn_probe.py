@@ -31,7 +31,7 @@ def _is(frag, name):
 
 def card():
     import torch
-    name = torch.cuda.get_device_name(0)
+    name = torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName     # (a driver may report no name)
     try:
         out = subprocess.run(['rocm-smi', '--showuniqueid'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=30).stdout
         ids = [ln.split(':')[-1].strip() for ln in out.splitlines() if 'Unique ID' in ln and 'GPU[' in ln]
