@@ -881,6 +881,9 @@ SN_EXPORT int sn_dpsroi_pool_bwd(const void *dout, const void *data, const float
   SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256 && sample_per_part <= kMaxS,
              "sn_dpsroi_pool_bwd: H, W < 65536, pooled <= 16 and sample_per_part <= %d required", kMaxS);
   SN_REQUIRE(!trans || d_trans, "sn_dpsroi_pool_bwd: d_trans required with trans");
+  const int cpr = C / 8;      // (checked before the first launch: a refused call must not have written d_data)
+  SN_REQUIRE(!trans || (C % 8 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0),
+             "sn_dpsroi_pool_bwd: with trans, C/8 must be a power of two <= 64 (C=%d)", C);
   hipStream_t s = sn_stream(stream);
   int4 *win = (int4 *)ws;
   hipLaunchKernelGGL(dpsroi_window_kernel, dim3(sn_div_up(R, 4)), dim3(256), 0, s, rois, trans, win, R, H, W, pooled,
@@ -896,9 +899,6 @@ SN_EXPORT int sn_dpsroi_pool_bwd(const void *dout, const void *data, const float
                        trans, (const int4 *)win, d_data, d_data_f32, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std);
   SN_CHECK_LAUNCH();
   if (trans) {
-    const int cpr = C / 8;
-    SN_REQUIRE(C % 8 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0,
-               "sn_dpsroi_pool_bwd: with trans, C/8 must be a power of two <= 64 (C=%d)", C);
     const long total = (long)R * pooled * pooled * cpr;
     if (pooled * pooled <= kBinsMax)
       hipLaunchKernelGGL((sample_per_part <= 4 ? dpsroi_bwd_trans_roi_kernel<4> : dpsroi_bwd_trans_roi_kernel<kMaxS>), dim3((unsigned)R),
@@ -1323,7 +1323,8 @@ SN_EXPORT int sn_psroi_pool_bwd(const void *dout, const void *data, const float 
                                 sn_stream_t stream) {
   SN_REQUIRE(dout && data && rois && d_data && ws && R > 0 && B > 0 && output_dim > 0 && group_size > 0 && pooled > 0 &&
                  sample_per_part > 0, "sn_psroi_pool_bwd: bad arguments");
-  SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256, "sn_psroi_pool_bwd: H, W < 65536 and pooled <= 16 required");
+  SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256 && sample_per_part <= kMaxS,
+             "sn_psroi_pool_bwd: H, W < 65536, pooled <= 16 and sample_per_part <= %d required", kMaxS);
   SN_REQUIRE(!trans || d_trans, "sn_psroi_pool_bwd: d_trans required with trans");
   const int C = output_dim * group_size * group_size;
   const long gz = (long)group_size * group_size * sn_div_up(output_dim, 256);

@@ -65,6 +65,43 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert '3x3' in str(e.value)
 
 
+def test_roi_pool_and_deform_argument_errors_are_reported_before_any_launch(lib):
+    """The limits of csrc/roi_deform.hip's dispatch, each refused by name before the first kernel of the call is launched (the
+    pointers are not dereferenced: there is no GPU here, a launch would fail with another message).  sample_per_part <= 8 holds
+    for all four pooling entry points: the offset gradient of sn_psroi_pool_bwd walks an eight-sample table, its data gradient
+    walked sample_per_part samples -- two gradients of two operators."""
+    from sniper_amd._lib import SniperHipError
+    p = ctypes.c_void_p(16)
+    sc, ts = 1.0 / 16, 0.1
+
+    def refused(words, name, *args):
+        with pytest.raises(SniperHipError) as e:
+            lib.call(name, *args)
+        msg = str(e.value)
+        assert all(w in msg for w in words), (name, msg)
+
+    # (dout, data, rois, trans, d_data, d_data_f32, d_trans, R, B, H, W, D, G, P, S, scale, trans_std, group_major, ws, stream)
+    refused(('sn_psroi_pool_bwd', 'sample_per_part <= 8'), 'sn_psroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 5, 3, 3, 9, sc, ts, 0, p, None)
+    refused(('sn_psroi_pool_bwd', 'sample_per_part <= 8'), 'sn_psroi_pool_bwd', p, p, p, None, p, 0, None, 4, 1, 12, 12, 5, 3, 3, 9, sc, ts, 1, p, None)
+    refused(('sn_psroi_pool_bwd', 'pooled <= 16'), 'sn_psroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 5, 1, 17, 4, sc, ts, 0, p, None)
+    refused(('sn_psroi_pool_fwd', 'sample_per_part <= 8'), 'sn_psroi_pool_fwd', p, p, p, p, 4, 12, 12, 5, 3, 3, 9, sc, ts, 0, None)
+    # (dout, data, rois, trans, d_data, d_data_f32, d_trans, R, B, H, W, C, P, S, scale, trans_std, ws, stream)
+    refused(('sn_dpsroi_pool_bwd', 'C/8 must be a power of two', 'C=24'), 'sn_dpsroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 24, 7, 4, sc, ts, p, None)
+    refused(('sn_dpsroi_pool_bwd', 'C/8 must be a power of two', 'C=12'), 'sn_dpsroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 12, 7, 4, sc, ts, p, None)
+    refused(('sn_dpsroi_pool_bwd', 'pooled <= 16'), 'sn_dpsroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 64, 17, 4, sc, ts, p, None)
+    refused(('sn_dpsroi_pool_bwd', 'sample_per_part <= 8'), 'sn_dpsroi_pool_bwd', p, p, p, p, p, 1, p, 4, 1, 12, 12, 64, 7, 9, sc, ts, p, None)
+    refused(('sn_dpsroi_pool_bwd', 'd_trans required'), 'sn_dpsroi_pool_bwd', p, p, p, p, p, 1, None, 4, 1, 12, 12, 64, 7, 4, sc, ts, p, None)
+    # (data, rois, trans, out, R, H, W, C, P, S, scale, trans_std, stream)
+    refused(('sn_dpsroi_pool_fwd', 'bad arguments'), 'sn_dpsroi_pool_fwd', p, p, p, p, 4, 12, 12, 12, 7, 4, sc, ts, None)
+    refused(('sn_dpsroi_pool_fwd', 'sample_per_part <= 8'), 'sn_dpsroi_pool_fwd', p, p, p, p, 4, 12, 12, 64, 7, 9, sc, ts, None)
+    refused(('sn_dpsroi_pool_fwd_images', 'B = 0'), 'sn_dpsroi_pool_fwd_images', p, p, p, p, 4, 0, 12, 12, 64, 7, 4, sc, ts, None)
+    # (dcol, data, offset, d_data, d_data_f32, d_offset, N, H, W, C, KH, KW, stride, pad, dil, DG, offset_pix_stride, offset_dtype, ws, stream)
+    refused(('sn_deform_col2im', 'power of two'), 'sn_deform_col2im', p, p, p, p, 1, p, 2, 14, 12, 96, 3, 3, 2, 1, 1, 4, 72, 1, None, None)
+    refused(('sn_deform_col2im', 'multiple of the deformable groups'), 'sn_deform_col2im', p, p, p, p, 1, None, 2, 14, 12, 64, 3, 3, 2, 1, 1,
+            3, 54, 1, None, None)
+    refused(('sn_deform_im2col', 'bad arguments'), 'sn_deform_im2col', p, p, p, 2, 14, 12, 36, 3, 3, 2, 1, 1, 3, 54, 1, None)
+
+
 def test_every_python_source_compiles():
     """Modules that only the -m gpu tests import must still be syntactically valid on the CPU tier."""
     bad = []
