@@ -194,6 +194,14 @@ struct BinWin {
   int x_lo, nx, y_lo, ny, slow;
   float inv;
 };
+// What the geometry phases of the two per-RoI kernels share (forward: BinWin; offset gradient: BinWinD, below): the cell window of
+// a bin with `count` valid samples; a window beyond kWinMax cells on an axis is `slow` (weights on the fly).
+template <typename BW, int SM>
+__device__ __forceinline__ void bin_window(BW &b, const AxisSamplesT<SM> &ax, const AxisSamplesT<SM> &ay, int count) {
+  b.x_lo = ax.lo; b.nx = count ? ax.hi - ax.lo + 1 : 0;
+  b.y_lo = ay.lo; b.ny = count ? ay.hi - ay.lo + 1 : 0;
+  b.slow = (b.nx > kWinMax || b.ny > kWinMax) ? 1 : 0;
+}
 template <int SM>
 __global__ __launch_bounds__(512) void dpsroi_fwd_roi_kernel(const half_t *__restrict__ data, const float *__restrict__ rois,
                                                              const float *__restrict__ trans, half_t *__restrict__ out, int R, int H,
@@ -208,9 +216,7 @@ __global__ __launch_bounds__(512) void dpsroi_fwd_roi_kernel(const half_t *__res
     BinWin &b = win[threadIdx.x];
     const int count = ax.n * ay.n;
     b.inv = count ? 1.f / (float)count : 0.f;
-    b.x_lo = ax.lo; b.nx = count ? ax.hi - ax.lo + 1 : 0;
-    b.y_lo = ay.lo; b.ny = count ? ay.hi - ay.lo + 1 : 0;
-    b.slow = (b.nx > kWinMax || b.ny > kWinMax) ? 1 : 0;
+    bin_window(b, ax, ay, count);
     if (!b.slow) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -308,11 +314,13 @@ __global__ __launch_bounds__(512) void dpsroi_fwd_roi_kernel(const half_t *__res
 // for 256 channels (one channel per thread, 16 fp32 accumulators in registers, written exactly once -> no zeroing,
 // no atomics, deterministic summation order):
 //   dpsroi_window_kernel : per RoI, the cell window its valid samples can touch (trans included);
-//   dpsroi_bwd_data_kernel: the tile scans the R windows (256 at a time, order-preserving ballot compaction), then
-//       phase A: one wave per RoI, one lane per bin -> separable weights of the bin on the tile's 4 columns / 4 rows
-//                (sum over the x-valid / y-valid samples of the bilinear tent; a sample counts iff both are valid, so
-//                the 4x4 sample grid factorises) -> compacted entry list in LDS;
-//       phase B: every thread (channel) walks the entries: one 2-byte load of dout, 16 FMAs.
+//   the four tile-owner kernels (dpsroi_bwd_data_kernel, dpsroi_bwd_data_mfma_kernel, psroi_ps_bwd_data_kernel<GM>) share
+//       the scan : tile_scan_rois -- the tile tests the R windows, 256 at a time, order-preserving ballot compaction;
+//       phase A  : bin_tile_weights, one lane per bin -> separable weights of the bin on the tile's 4 columns / 4 rows
+//                  (sum over the x-valid / y-valid samples of the bilinear tent; a sample counts iff both are valid, so
+//                  the S x S sample grid factorises) -> entry list in LDS, compacted in wave order (wave_prefix4);
+//       phase B  : every thread (channel) walks the entries: one 2-byte load of dout, 16 FMAs (the MFMA kernel: a GEMM);
+//     they differ in who owns which channels, which (RoI, bin) items a workgroup walks and how phase B multiplies.
 //   dpsroi_bwd_trans_kernel: d_trans is a gather (like the forward), reduced over the channels with shuffles.
 // adds the bilinear weights of the (already clamped) coordinate w onto the 4 tile cells t0..t0+3
 __device__ __forceinline__ void tent4(float w, int t0, float W4[4]) {
@@ -320,6 +328,70 @@ __device__ __forceinline__ void tent4(float w, int t0, float W4[4]) {
   const float d = w - (float)a;
 #pragma unroll
   for (int k = 0; k < 4; ++k) W4[k] += (a - t0 == k ? 1.f - d : 0.f) + (b - t0 == k ? d : 0.f);
+}
+
+// origin (first column, first row) of the 4x4-cell tile that workgroup blockIdx.x owns
+__device__ __forceinline__ void tile_origin(int W, int &x0, int &y0) {
+  const int tiles_x = (W + 3) >> 2;
+  x0 = (int)(blockIdx.x % tiles_x) * 4;
+  y0 = (int)(blockIdx.x / tiles_x) * 4;
+}
+
+// does the cell window w of a RoI (dpsroi_window_kernel) touch the tile at (x0, y0) of image b?
+__device__ __forceinline__ bool window_hits_tile(const int4 w, int b, int x0, int y0) {
+  return w.w && w.x == b && (w.y & 0xffff) <= x0 + 3 && (w.y >> 16) >= x0 && (w.z & 0xffff) <= y0 + 3 && (w.z >> 16) >= y0;
+}
+
+// cnt[0..3] = what each of the workgroup's four waves contributes: off = the sum over the waves before this one, total = over all
+__device__ __forceinline__ void wave_prefix4(const int *cnt, int wave, int &off, int &total) {
+  off = 0;
+  total = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int n = cnt[k];
+    off += k < wave ? n : 0;
+    total += n;
+  }
+}
+
+// RoIs base .. base + 255 (one per thread) whose window touches the tile, compacted in order into roi_list (LDS, 256 ints; wave_cnt:
+// LDS, 4 ints); returns their number.  BOTH workgroup barriers are in here -- counts visible, then list visible -- so every thread
+// of the workgroup must call it, from uniform control flow.
+__device__ __forceinline__ int tile_scan_rois(const int4 *__restrict__ win, int base, int R, int b, int x0, int y0, int *roi_list,
+                                              int *wave_cnt) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rr = base + (int)threadIdx.x;
+  const bool hit = rr < R && window_hits_tile(win[rr], b, x0, y0);
+  const unsigned long long m = __ballot(hit);
+  if (lane == 0) wave_cnt[wave] = __popcll(m);
+  __syncthreads();
+  int off, total;
+  wave_prefix4(wave_cnt, wave, off, total);
+  if (hit) roi_list[off + __popcll(m & ((1ull << lane) - 1ull))] = rr;
+  __syncthreads();
+  return total;
+}
+
+// Separable weights of the bin with geometry g on the tile's 4 columns (Wx) and 4 rows (Wy), both zero on entry: the tents of the
+// x-valid / y-valid samples.  inv = 1 / (valid samples of the bin); returns whether the bin puts any weight on the tile.
+__device__ __forceinline__ bool bin_tile_weights(const RoiGeom &g, int S, int H, int W, int x0, int y0, float Wx[4], float Wy[4],
+                                                 float &inv) {
+  int nvx = 0, nvy = 0;
+  for (int i = 0; i < S; ++i) {
+    float w = sample_pos(g.wstart, i, g.sub_w), h = sample_pos(g.hstart, i, g.sub_h);
+    if (!(w < -0.5f || w > (float)W - 0.5f)) {
+      ++nvx;
+      tent4(fminf(fmaxf(w, 0.f), (float)W - 1.f), x0, Wx);
+    }
+    if (!(h < -0.5f || h > (float)H - 0.5f)) {
+      ++nvy;
+      tent4(fminf(fmaxf(h, 0.f), (float)H - 1.f), y0, Wy);
+    }
+  }
+  const float sx = Wx[0] + Wx[1] + Wx[2] + Wx[3], sy = Wy[0] + Wy[1] + Wy[2] + Wy[3];
+  const bool act = nvx * nvy > 0 && sx > 0.f && sy > 0.f;
+  inv = act ? 1.f / (float)(nvx * nvy) : 0.f;
+  return act;
 }
 
 // One wave per RoI, one lane per bin (P * P <= 64; a lane walks several bins beyond that), min / max over the wave by shuffles: the
@@ -370,7 +442,19 @@ __global__ __launch_bounds__(256) void dpsroi_window_kernel(const float *__restr
 
 constexpr int kEntStride = 12;  // floats per LDS entry: [index, -, -, - | Wx[4] (already / count) | Wy[4]]
 
-// acc[cy*4+cx] += Wy[cy] * Wx[cx] * dv for the entries [0, n) of one segment
+// acc[cy*4+cx] += Wy[cy] * Wx[cx] * dv for the entry at q
+__device__ __forceinline__ void tile_fma(const float *__restrict__ q, float dv, float acc[16]) {
+  const float4 wx = *reinterpret_cast<const float4 *>(q + 4);
+  const float4 wy = *reinterpret_cast<const float4 *>(q + 8);
+  const float X[4] = {wx.x * dv, wx.y * dv, wx.z * dv, wx.w * dv};
+  const float Y[4] = {wy.x, wy.y, wy.z, wy.w};
+#pragma unroll
+  for (int cy = 0; cy < 4; ++cy)
+#pragma unroll
+    for (int cx = 0; cx < 4; ++cx) acc[cy * 4 + cx] += Y[cy] * X[cx];
+}
+
+// the same for the entries [0, n) of one segment, dv = src[index of the entry][c]
 template <typename TD>
 __device__ __forceinline__ void tile_accumulate(const float *__restrict__ ent, int n, const TD *__restrict__ src, size_t C, int c,
                                                 bool active_c, float acc[16]) {
@@ -383,28 +467,11 @@ __device__ __forceinline__ void tile_accumulate(const float *__restrict__ ent, i
       dv[u] = active_c ? (float)src[(size_t)idx * C + c] : 0.f;
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 wx = *reinterpret_cast<const float4 *>(ent + (e + u) * kEntStride + 4);
-      const float4 wy = *reinterpret_cast<const float4 *>(ent + (e + u) * kEntStride + 8);
-      const float X[4] = {wx.x * dv[u], wx.y * dv[u], wx.z * dv[u], wx.w * dv[u]};
-      const float Y[4] = {wy.x, wy.y, wy.z, wy.w};
-#pragma unroll
-      for (int cy = 0; cy < 4; ++cy)
-#pragma unroll
-        for (int cx = 0; cx < 4; ++cx) acc[cy * 4 + cx] += Y[cy] * X[cx];
-    }
+    for (int u = 0; u < 4; ++u) tile_fma(ent + (e + u) * kEntStride, dv[u], acc);
   }
   for (; e < n; ++e) {
     const int idx = __float_as_int(ent[e * kEntStride]);
-    const float dv = active_c ? (float)src[(size_t)idx * C + c] : 0.f;
-    const float4 wx = *reinterpret_cast<const float4 *>(ent + e * kEntStride + 4);
-    const float4 wy = *reinterpret_cast<const float4 *>(ent + e * kEntStride + 8);
-    const float X[4] = {wx.x * dv, wx.y * dv, wx.z * dv, wx.w * dv};
-    const float Y[4] = {wy.x, wy.y, wy.z, wy.w};
-#pragma unroll
-    for (int cy = 0; cy < 4; ++cy)
-#pragma unroll
-      for (int cx = 0; cx < 4; ++cx) acc[cy * 4 + cx] += Y[cy] * X[cx];
+    tile_fma(ent + e * kEntStride, active_c ? (float)src[(size_t)idx * C + c] : 0.f, acc);
   }
 }
 
@@ -435,32 +502,15 @@ __global__ __launch_bounds__(256) void dpsroi_bwd_data_kernel(const half_t *__re
   int *seg_n = wave_cnt + 4;                                         // [4]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  const int tiles_x = (W + 3) >> 2;
-  const int x0 = (int)(blockIdx.x % tiles_x) * 4, y0 = (int)(blockIdx.x / tiles_x) * 4;
+  int x0, y0;
+  tile_origin(W, x0, y0);
   const int b = blockIdx.y, c = blockIdx.z * 256 + tid;
   const bool active_c = c < C;
   float acc[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) acc[k] = 0.f;
   for (int base = 0; base < R; base += 256) {
-    const int rr = base + tid;
-    bool hit = false;
-    if (rr < R) {
-      const int4 w = win[rr];
-      hit = w.w && w.x == b && (w.y & 0xffff) <= x0 + 3 && (w.y >> 16) >= x0 && (w.z & 0xffff) <= y0 + 3 && (w.z >> 16) >= y0;
-    }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int n = wave_cnt[k];
-      off += k < wave ? n : 0;
-      total += n;
-    }
-    if (hit) roi_list[off + __popcll(m & lt)] = rr;
-    __syncthreads();
+    const int total = tile_scan_rois(win, base, R, b, x0, y0, roi_list, wave_cnt);
     for (int g0 = 0; g0 < total; g0 += 4) {
       int n_e = 0;
       if (g0 + wave < total) {                                       // phase A: this wave's RoI, one lane per bin
@@ -472,22 +522,7 @@ __global__ __launch_bounds__(256) void dpsroi_bwd_data_kernel(const half_t *__re
           float inv = 0.f;
           if (bin < PP) {
             const int ph = bin / P, pw = bin - ph * P;
-            const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-            int nvx = 0, nvy = 0;
-            for (int i = 0; i < S; ++i) {
-              float w = sample_pos(g.wstart, i, g.sub_w), h = sample_pos(g.hstart, i, g.sub_h);
-              if (!(w < -0.5f || w > (float)W - 0.5f)) {
-                ++nvx;
-                tent4(fminf(fmaxf(w, 0.f), (float)W - 1.f), x0, Wx);
-              }
-              if (!(h < -0.5f || h > (float)H - 0.5f)) {
-                ++nvy;
-                tent4(fminf(fmaxf(h, 0.f), (float)H - 1.f), y0, Wy);
-              }
-            }
-            const float sx = Wx[0] + Wx[1] + Wx[2] + Wx[3], sy = Wy[0] + Wy[1] + Wy[2] + Wy[3];
-            act = nvx * nvy > 0 && sx > 0.f && sy > 0.f;
-            inv = act ? 1.f / (float)(nvx * nvy) : 0.f;
+            act = bin_tile_weights(roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std), S, H, W, x0, y0, Wx, Wy, inv);
           }
           const unsigned long long am = __ballot(act);
           if (act) {
@@ -536,8 +571,8 @@ __global__ __launch_bounds__(256, 5) void dpsroi_bwd_data_mfma_kernel(const half
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, kg = lane >> 4;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  const int tiles_x = (W + 3) >> 2;
-  const int x0 = (int)(blockIdx.x % tiles_x) * 4, y0 = (int)(blockIdx.x / tiles_x) * 4;
+  int x0, y0;
+  tile_origin(W, x0, y0);
   const int b = blockIdx.y, c0 = blockIdx.z * 256 + wave * 64;
   floatx4 acc[4];
 #pragma unroll
@@ -577,24 +612,7 @@ __global__ __launch_bounds__(256, 5) void dpsroi_bwd_data_mfma_kernel(const half
     cnt = 0;
   };
   for (int base = 0; base < R; base += 256) {
-    const int rr = base + tid;
-    bool hit = false;
-    if (rr < R) {
-      const int4 w = win[rr];
-      hit = w.w && w.x == b && (w.y & 0xffff) <= x0 + 3 && (w.y >> 16) >= x0 && (w.z & 0xffff) <= y0 + 3 && (w.z >> 16) >= y0;
-    }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int n = wave_cnt[k];
-      off += k < wave ? n : 0;
-      total += n;
-    }
-    if (hit) roi_list[off + __popcll(m & lt)] = rr;
-    __syncthreads();
+    const int total = tile_scan_rois(win, base, R, b, x0, y0, roi_list, wave_cnt);
     for (int g0 = 0; g0 < total; g0 += 4) {
       if (cnt > kListCap - 4 * kMfmaK) flush();                      // room for four more RoIs?
       // phase A: this wave's RoI, one lane per bin -> which bins touch the tile, and their separable weights
@@ -606,35 +624,15 @@ __global__ __launch_bounds__(256, 5) void dpsroi_bwd_data_mfma_kernel(const half
       if (g0 + wave < total && bin < PP) {
         r = roi_list[g0 + wave];
         const int ph = bin / P, pw = bin - ph * P;
-        const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-        int nvx = 0, nvy = 0;
-        for (int i = 0; i < S; ++i) {
-          float w = sample_pos(g.wstart, i, g.sub_w), h = sample_pos(g.hstart, i, g.sub_h);
-          if (!(w < -0.5f || w > (float)W - 0.5f)) {
-            ++nvx;
-            tent4(fminf(fmaxf(w, 0.f), (float)W - 1.f), x0, Wx);
-          }
-          if (!(h < -0.5f || h > (float)H - 0.5f)) {
-            ++nvy;
-            tent4(fminf(fmaxf(h, 0.f), (float)H - 1.f), y0, Wy);
-          }
-        }
-        const float sx = Wx[0] + Wx[1] + Wx[2] + Wx[3], sy = Wy[0] + Wy[1] + Wy[2] + Wy[3];
-        act = nvx * nvy > 0 && sx > 0.f && sy > 0.f;
-        inv = act ? 1.f / (float)(nvx * nvy) : 0.f;
+        act = bin_tile_weights(roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std), S, H, W, x0, y0, Wx, Wy, inv);
       }
       const unsigned long long am = __ballot(act);
       if (lane == 0) seg_n[wave] = __popcll(am);
       __syncthreads();
-      int eoff = cnt, added = 0;      // entries of the four RoIs are appended in wave order
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int n = seg_n[k];
-        eoff += k < wave ? n : 0;
-        added += n;
-      }
+      int eoff, added;                // entries of the four RoIs are appended in wave order
+      wave_prefix4(seg_n, wave, eoff, added);
       if (act) {
-        const int pos = eoff + __popcll(am & lt);
+        const int pos = cnt + eoff + __popcll(am & lt);
         e_row[pos] = r * PP + bin;
 #pragma unroll
         for (int cy = 0; cy < 4; ++cy)
@@ -672,6 +670,27 @@ __global__ __launch_bounds__(256, 5) void dpsroi_bwd_data_mfma_kernel(const half
 // that share a bin, one plain store per (r,ph,pw,xy).  Same window factorisation as the forward:
 //   d out / d tx = roi_w * trans_std / count * sum_y sum_x Wy(y) DWx(x) data[y][x],  DWx = +1 / -1 on a sample's upper / lower cell
 // (and x <-> y for ty), so each cell of the window is read once for both derivatives.
+// The window walk with the weights computed on the fly: gtx += Wy(y) DWx(x) <data[y][x], go>, gty += DWy(y) Wx(x) <data[y][x], go>
+// over a lane's eight channels (img points at them in cell (0, 0)).  The plain eight-term dot, not dot8: the two round differently.
+template <int SM>
+__device__ __forceinline__ void trans_window_walk(const AxisSamplesT<SM> &ax, const AxisSamplesT<SM> &ay, const half_t *__restrict__ img,
+                                                  int W, int C, half8 go, float &gtx, float &gty) {
+  for (int y = ay.lo; y <= ay.hi; ++y) {
+    const float wy = tent_sum(ay, y), dwy = tent_dsum(ay, y);
+    if (wy == 0.f && dwy == 0.f) continue;
+    for (int x = ax.lo; x <= ax.hi; ++x) {
+      const float kx = wy * tent_dsum(ax, x), ky = dwy * tent_sum(ax, x);
+      if (kx == 0.f && ky == 0.f) continue;
+      const half8 u = *reinterpret_cast<const half8 *>(img + ((size_t)y * W + x) * C);
+      float dot = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dot += (float)u[j] * (float)go[j];
+      gtx += kx * dot;
+      gty += ky * dot;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void dpsroi_bwd_trans_kernel(const half_t *__restrict__ dout, const half_t *__restrict__ data,
                                                                const float *__restrict__ rois, const float *__restrict__ trans,
                                                                float *__restrict__ d_trans, int R, int H, int W, int C, int P, int S,
@@ -692,24 +711,7 @@ __global__ __launch_bounds__(256) void dpsroi_bwd_trans_kernel(const half_t *__r
   const half8 go = *reinterpret_cast<const half8 *>(dout + ii * 8);
   float gtx = 0.f, gty = 0.f;
   const int count = ax.n * ay.n;
-  if (count) {
-    for (int y = ay.lo; y <= ay.hi; ++y) {
-      const float wy = tent_sum(ay, y), dwy = tent_dsum(ay, y);
-      if (wy == 0.f && dwy == 0.f) continue;
-      const half_t *row = img + (size_t)y * W * C;
-      for (int x = ax.lo; x <= ax.hi; ++x) {
-        const float wx = tent_sum(ax, x), dwx = tent_dsum(ax, x);
-        const float kx = wy * dwx, ky = dwy * wx;
-        if (kx == 0.f && ky == 0.f) continue;
-        const half8 u = *reinterpret_cast<const half8 *>(row + (size_t)x * C);
-        float dot = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dot += (float)u[j] * (float)go[j];
-        gtx += kx * dot;
-        gty += ky * dot;
-      }
-    }
-  }
+  if (count) trans_window_walk(ax, ay, img, W, C, go, gtx, gty);
   const float k = count ? trans_std / (float)count : 0.f;
   gtx *= k * g.roi_w;
   gty *= k * g.roi_h;
@@ -754,9 +756,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const float k = count ? trans_std / (float)count : 0.f;
     b.kx = k * g.roi_w;
     b.ky = k * g.roi_h;
-    b.x_lo = ax.lo; b.nx = count ? ax.hi - ax.lo + 1 : 0;
-    b.y_lo = ay.lo; b.ny = count ? ay.hi - ay.lo + 1 : 0;
-    b.slow = (b.nx > kWinMax || b.ny > kWinMax) ? 1 : 0;
+    bin_window(b, ax, ay, count);
     if (!b.slow) {
       auto weights = [&](int q) {
         b.wx[q] = q < b.nx ? tent_sum(ax, ax.lo + q) : 0.f;
@@ -804,24 +804,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             gty += ky * dot;
           }
         }
-      } else {             // oversized window: weights on the fly, as dpsroi_bwd_trans_kernel
+      } else {             // oversized window: weights on the fly, the walk of dpsroi_bwd_trans_kernel
         const int ph = bin / P, pw = bin - ph * P;
         const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
         const AxisSamplesT<SM> ax = axis_samples<SM>(g.wstart, g.sub_w, S, W), ay = axis_samples<SM>(g.hstart, g.sub_h, S, H);
-        for (int y = ay.lo; y <= ay.hi; ++y) {
-          const float wy = tent_sum(ay, y), dwy = tent_dsum(ay, y);
-          if (wy == 0.f && dwy == 0.f) continue;
-          for (int x = ax.lo; x <= ax.hi; ++x) {
-            const float kx = wy * tent_dsum(ax, x), ky = dwy * tent_sum(ax, x);
-            if (kx == 0.f && ky == 0.f) continue;
-            const half8 u = *reinterpret_cast<const half8 *>(img + ((size_t)y * W + x) * C);
-            float dot = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) dot += (float)u[j] * (float)go[j];
-            gtx += kx * dot;
-            gty += ky * dot;
-          }
-        }
+        trans_window_walk(ax, ay, img, W, C, go, gtx, gty);
       }
       gtx *= b.kx;
       gty *= b.ky;
@@ -873,22 +860,40 @@ SN_EXPORT int sn_dpsroi_pool_fwd_images(const void *data, const float *rois, con
 
 SN_EXPORT size_t sn_dpsroi_bwd_workspace_bytes(int R) { return sn_align(sizeof(int4) * (size_t)(R > 0 ? R : 1)); }
 
+// what both backward entry points (`who`, for the message) require of the arguments they have in common; `dims_ok`: the caller's own
+// sizes (C, or output_dim and group_size) are positive
+static int roi_bwd_check(const char *who, bool dims_ok, const void *dout, const void *data, const float *rois, const float *trans,
+                         const void *d_data, const float *d_trans, const void *ws, int R, int B, int H, int W, int pooled,
+                         int sample_per_part) {
+  SN_REQUIRE(dout && data && rois && d_data && ws && R > 0 && B > 0 && dims_ok && pooled > 0 && sample_per_part > 0,
+             "%s: bad arguments", who);
+  SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256 && sample_per_part <= kMaxS,
+             "%s: H, W < 65536, pooled <= 16 and sample_per_part <= %d required", who, kMaxS);
+  SN_REQUIRE(!trans || d_trans, "%s: d_trans required with trans", who);
+  return SN_OK;
+}
+
+// first launch of both backward passes: every RoI's cell window into the workspace
+static int roi_bwd_windows(const float *rois, const float *trans, int4 *win, int R, int H, int W, int pooled, int sample_per_part,
+                           float spatial_scale, float trans_std, hipStream_t s) {
+  hipLaunchKernelGGL(dpsroi_window_kernel, dim3(sn_div_up(R, 4)), dim3(256), 0, s, rois, trans, win, R, H, W, pooled,
+                     sample_per_part, spatial_scale, trans_std);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
 SN_EXPORT int sn_dpsroi_pool_bwd(const void *dout, const void *data, const float *rois, const float *trans, void *d_data,
                                  int d_data_f32, float *d_trans, int R, int B, int H, int W, int C, int pooled,
                                  int sample_per_part, float spatial_scale, float trans_std, void *ws, sn_stream_t stream) {
-  SN_REQUIRE(dout && data && rois && d_data && ws && R > 0 && B > 0 && C > 0 && pooled > 0 && sample_per_part > 0,
-             "sn_dpsroi_pool_bwd: bad arguments");
-  SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256 && sample_per_part <= kMaxS,
-             "sn_dpsroi_pool_bwd: H, W < 65536, pooled <= 16 and sample_per_part <= %d required", kMaxS);
-  SN_REQUIRE(!trans || d_trans, "sn_dpsroi_pool_bwd: d_trans required with trans");
+  if (const int e = roi_bwd_check("sn_dpsroi_pool_bwd", C > 0, dout, data, rois, trans, d_data, d_trans, ws, R, B, H, W, pooled,
+                                  sample_per_part))
+    return e;
   const int cpr = C / 8;      // (checked before the first launch: a refused call must not have written d_data)
   SN_REQUIRE(!trans || (C % 8 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0),
              "sn_dpsroi_pool_bwd: with trans, C/8 must be a power of two <= 64 (C=%d)", C);
   hipStream_t s = sn_stream(stream);
   int4 *win = (int4 *)ws;
-  hipLaunchKernelGGL(dpsroi_window_kernel, dim3(sn_div_up(R, 4)), dim3(256), 0, s, rois, trans, win, R, H, W, pooled,
-                     sample_per_part, spatial_scale, trans_std);
-  SN_CHECK_LAUNCH();
+  if (const int e = roi_bwd_windows(rois, trans, win, R, H, W, pooled, sample_per_part, spatial_scale, trans_std, s)) return e;
   const int tiles = sn_div_up(W, 4) * sn_div_up(H, 4);
   const size_t smem = sizeof(float) * 4 * pooled * pooled * kEntStride + sizeof(int) * (256 + 8);
   if (pooled * pooled <= kMfmaK)      // entries x channels on the matrix cores (larger bin grids: the scalar tile-owner kernel)
@@ -988,9 +993,17 @@ __global__ __launch_bounds__(256) void psroi_ps_fwd_kernel(const half_t *__restr
   }
 }
 
-// Data gradient, tile-owned like dpsroi_bwd_data_kernel: a workgroup owns (4x4-cell tile, image, group (gh,gw), 256
-// output channels d) = the map channels (d*G+gh)*G+gw of that tile, and walks the (RoI, bin) items whose bin maps to
-// its group, 256 items per round (one per thread) compacted in order into the LDS entry list.
+// Data gradient, tile-owned like dpsroi_bwd_data_kernel: a workgroup owns a 4x4-cell tile of one image for 256 map channels (one per
+// thread) and walks the (RoI, bin) items whose bin maps to a group it covers, 256 items per round (one per thread) compacted in
+// order into the LDS entry list.
+// GM = false, the operator's own channel order: the workgroup owns (group (gh,gw), 256 output channels d) = the map channels
+// (d*G+gh)*G+gw of that tile, and walks the bins of that one group.
+// GM = true, group-major layout (gm = 1): the workgroup owns 256 CONSECUTIVE map channels c = grp*D + d.  Those channels span
+// ceil(256 / D) + 1 bin groups at most (D = 81: four; D = 4 or 2: all 49), so the workgroup walks the (RoI, bin) items of every
+// group it covers once, each entry carries its group, and a thread accumulates the entries of its own group.  Against the operator-
+// order form: 16 instead of 49 channel slices for D = 81 with every lane active (81 of 256 there), ONE slice instead of 49 for the
+// D = 4 / D = 2 maps (4 / 2 active lanes of 256 there); stores of a wave are one contiguous run.
+template <bool GM>
 __global__ __launch_bounds__(256) void psroi_ps_bwd_data_kernel(const half_t *__restrict__ dout, const float *__restrict__ rois,
                                                                 const float *__restrict__ trans, const int4 *__restrict__ win,
                                                                 void *__restrict__ d_data, int out_f32, int R, int H, int W, int C,
@@ -1002,120 +1015,26 @@ __global__ __launch_bounds__(256) void psroi_ps_bwd_data_kernel(const half_t *__
   const int PP = P * P;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  const int tiles_x = (W + 3) >> 2;
-  const int x0 = (int)(blockIdx.x % tiles_x) * 4, y0 = (int)(blockIdx.x / tiles_x) * 4;
+  int x0, y0;
+  tile_origin(W, x0, y0);
   const int b = blockIdx.y;
-  const int chunks = (D + 255) >> 8;
-  const int grp = blockIdx.z / chunks, d = (blockIdx.z % chunks) * 256 + tid;
-  const int gh = grp / G, gw = grp % G;
-  const bool active_c = d < D;
-  if (tid == 0) {
-    int n = 0;
-    for (int bin = 0; bin < PP; ++bin)
-      if (ps_group(bin / P, G, P) == gh && ps_group(bin % P, G, P) == gw) bins[n++] = bin;
-    nb_s = n;
+  // this thread's map channel c = output channel d of group mygrp; the workgroup walks the bins of the groups g_lo .. g_hi
+  int c, d, mygrp, g_lo, g_hi;
+  bool active_c;
+  if constexpr (GM) {
+    c = blockIdx.z * 256 + tid;
+    active_c = c < C;
+    mygrp = active_c ? c / D : -1;
+    d = active_c ? c - mygrp * D : 0;
+    g_lo = (blockIdx.z * 256) / D;
+    g_hi = min(G * G - 1, (blockIdx.z * 256 + 255) / D);
+  } else {
+    const int chunks = (D + 255) >> 8;
+    mygrp = g_lo = g_hi = blockIdx.z / chunks;
+    d = (blockIdx.z % chunks) * 256 + tid;
+    active_c = d < D;
+    c = (d * G + mygrp / G) * G + mygrp % G;
   }
-  __syncthreads();
-  const int nb = nb_s;
-  float acc[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-  if (nb > 0) {
-    for (int base = 0; base < R; base += 256) {
-      const int rr = base + tid;
-      bool hit = false;
-      if (rr < R) {
-        const int4 w = win[rr];
-        hit = w.w && w.x == b && (w.y & 0xffff) <= x0 + 3 && (w.y >> 16) >= x0 && (w.z & 0xffff) <= y0 + 3 && (w.z >> 16) >= y0;
-      }
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) wave_cnt[wave] = __popcll(m);
-      __syncthreads();
-      int off = 0, total = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int n = wave_cnt[k];
-        off += k < wave ? n : 0;
-        total += n;
-      }
-      if (hit) roi_list[off + __popcll(m & lt)] = rr;
-      __syncthreads();
-      const int nitems = total * nb;
-      for (int it0 = 0; it0 < nitems; it0 += 256) {
-        const int item = it0 + tid;
-        bool act = false;
-        float Wx[4] = {0.f, 0.f, 0.f, 0.f}, Wy[4] = {0.f, 0.f, 0.f, 0.f};
-        float inv = 0.f;
-        int idx = 0;
-        if (item < nitems) {
-          const int r = roi_list[item / nb], bin = bins[item % nb];
-          const int ph = bin / P, pw = bin - ph * P;
-          const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-          int nvx = 0, nvy = 0;
-          for (int i = 0; i < S; ++i) {
-            float w = sample_pos(g.wstart, i, g.sub_w), h = sample_pos(g.hstart, i, g.sub_h);
-            if (!(w < -0.5f || w > (float)W - 0.5f)) {
-              ++nvx;
-              tent4(fminf(fmaxf(w, 0.f), (float)W - 1.f), x0, Wx);
-            }
-            if (!(h < -0.5f || h > (float)H - 0.5f)) {
-              ++nvy;
-              tent4(fminf(fmaxf(h, 0.f), (float)H - 1.f), y0, Wy);
-            }
-          }
-          const float sx = Wx[0] + Wx[1] + Wx[2] + Wx[3], sy = Wy[0] + Wy[1] + Wy[2] + Wy[3];
-          act = nvx * nvy > 0 && sx > 0.f && sy > 0.f;
-          inv = act ? 1.f / (float)(nvx * nvy) : 0.f;
-          idx = r * PP + bin;
-        }
-        const unsigned long long am = __ballot(act);
-        if (lane == 0) ent_cnt[wave] = __popcll(am);
-        __syncthreads();
-        int eoff = 0, n_e = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int n = ent_cnt[k];
-          eoff += k < wave ? n : 0;
-          n_e += n;
-        }
-        if (act) {
-          float *e = ent + (size_t)(eoff + __popcll(am & lt)) * kEntStride;
-          e[0] = __int_as_float(idx);
-          *reinterpret_cast<float4 *>(e + 4) = make_float4(Wx[0] * inv, Wx[1] * inv, Wx[2] * inv, Wx[3] * inv);
-          *reinterpret_cast<float4 *>(e + 8) = make_float4(Wy[0], Wy[1], Wy[2], Wy[3]);
-        }
-        __syncthreads();
-        tile_accumulate<half_t>(ent, n_e, dout, (size_t)D, d, active_c, acc);
-        __syncthreads();
-      }
-    }
-  }
-  if (active_c) tile_store(acc, d_data, out_f32, b, y0, x0, H, W, C, (d * G + gh) * G + gw);
-}
-
-// Group-major layout (gm = 1): a workgroup owns (4x4-cell tile, image, 256 CONSECUTIVE map channels c = grp*D + d).  Those channels
-// span ceil(256 / D) + 1 bin groups at most (D = 81: four; D = 4 or 2: all 49), so the workgroup walks the (RoI, bin) items of every
-// group it covers once, each entry carries its group, and a thread accumulates the entries of its own group.  Against the operator-
-// order kernel above: 16 instead of 49 channel slices for D = 81 with every lane active (81 of 256 there), ONE slice instead of 49
-// for the D = 4 / D = 2 maps (4 / 2 active lanes of 256 there); stores of a wave are one contiguous run.
-__global__ __launch_bounds__(256) void psroi_ps_bwd_data_gm_kernel(const half_t *__restrict__ dout, const float *__restrict__ rois,
-                                                                   const float *__restrict__ trans, const int4 *__restrict__ win,
-                                                                   void *__restrict__ d_data, int out_f32, int R, int H, int W, int C,
-                                                                   int P, int S, int G, int D, float scale, float trans_std) {
-  __shared__ __attribute__((aligned(16))) float ent[256 * kEntStride];
-  __shared__ int roi_list[256];
-  __shared__ int bins[256];
-  __shared__ int wave_cnt[4], ent_cnt[4], nb_s;
-  const int PP = P * P;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  const int tiles_x = (W + 3) >> 2;
-  const int x0 = (int)(blockIdx.x % tiles_x) * 4, y0 = (int)(blockIdx.x / tiles_x) * 4;
-  const int b = blockIdx.y;
-  const int c = blockIdx.z * 256 + tid;          // this thread's map channel
-  const bool active_c = c < C;
-  const int mygrp = active_c ? c / D : -1, d = active_c ? c - mygrp * D : 0;
-  const int g_lo = (blockIdx.z * 256) / D, g_hi = min(G * G - 1, (blockIdx.z * 256 + 255) / D);
   if (tid == 0) {
     int n = 0;
     for (int bin = 0; bin < PP; ++bin) {
@@ -1131,24 +1050,7 @@ __global__ __launch_bounds__(256) void psroi_ps_bwd_data_gm_kernel(const half_t 
   for (int k = 0; k < 16; ++k) acc[k] = 0.f;
   if (nb > 0) {
     for (int base = 0; base < R; base += 256) {
-      const int rr = base + tid;
-      bool hit = false;
-      if (rr < R) {
-        const int4 w = win[rr];
-        hit = w.w && w.x == b && (w.y & 0xffff) <= x0 + 3 && (w.y >> 16) >= x0 && (w.z & 0xffff) <= y0 + 3 && (w.z >> 16) >= y0;
-      }
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) wave_cnt[wave] = __popcll(m);
-      __syncthreads();
-      int off = 0, total = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int n = wave_cnt[k];
-        off += k < wave ? n : 0;
-        total += n;
-      }
-      if (hit) roi_list[off + __popcll(m & lt)] = rr;
-      __syncthreads();
+      const int total = tile_scan_rois(win, base, R, b, x0, y0, roi_list, wave_cnt);
       const int nitems = total * nb;
       for (int it0 = 0; it0 < nitems; it0 += 256) {
         const int item = it0 + tid;
@@ -1159,54 +1061,31 @@ __global__ __launch_bounds__(256) void psroi_ps_bwd_data_gm_kernel(const half_t 
         if (item < nitems) {
           const int r = roi_list[item / nb], bin = bins[item % nb];
           const int ph = bin / P, pw = bin - ph * P;
-          grp = ps_group(ph, G, P) * G + ps_group(pw, G, P);
-          const RoiGeom g = roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std);
-          int nvx = 0, nvy = 0;
-          for (int i = 0; i < S; ++i) {
-            float w = sample_pos(g.wstart, i, g.sub_w), h = sample_pos(g.hstart, i, g.sub_h);
-            if (!(w < -0.5f || w > (float)W - 0.5f)) {
-              ++nvx;
-              tent4(fminf(fmaxf(w, 0.f), (float)W - 1.f), x0, Wx);
-            }
-            if (!(h < -0.5f || h > (float)H - 0.5f)) {
-              ++nvy;
-              tent4(fminf(fmaxf(h, 0.f), (float)H - 1.f), y0, Wy);
-            }
-          }
-          const float sx = Wx[0] + Wx[1] + Wx[2] + Wx[3], sy = Wy[0] + Wy[1] + Wy[2] + Wy[3];
-          act = nvx * nvy > 0 && sx > 0.f && sy > 0.f;
-          inv = act ? 1.f / (float)(nvx * nvy) : 0.f;
+          if constexpr (GM) grp = ps_group(ph, G, P) * G + ps_group(pw, G, P);
+          act = bin_tile_weights(roi_geom(rois, trans, r, ph, pw, P, S, scale, trans_std), S, H, W, x0, y0, Wx, Wy, inv);
           idx = r * PP + bin;
         }
         const unsigned long long am = __ballot(act);
         if (lane == 0) ent_cnt[wave] = __popcll(am);
         __syncthreads();
-        int eoff = 0, n_e = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int n = ent_cnt[k];
-          eoff += k < wave ? n : 0;
-          n_e += n;
-        }
+        int eoff, n_e;
+        wave_prefix4(ent_cnt, wave, eoff, n_e);
         if (act) {
           float *e = ent + (size_t)(eoff + __popcll(am & lt)) * kEntStride;
           e[0] = __int_as_float(idx);
-          e[1] = __int_as_float(grp);
+          if constexpr (GM) e[1] = __int_as_float(grp);
           *reinterpret_cast<float4 *>(e + 4) = make_float4(Wx[0] * inv, Wx[1] * inv, Wx[2] * inv, Wx[3] * inv);
           *reinterpret_cast<float4 *>(e + 8) = make_float4(Wy[0], Wy[1], Wy[2], Wy[3]);
         }
         __syncthreads();
-        for (int e = 0; e < n_e; ++e) {           // entries in list order: fixed summation order per channel
-          const float *q = ent + e * kEntStride;
-          if (__float_as_int(q[1]) != mygrp) continue;
-          const float dv = (float)dout[(size_t)__float_as_int(q[0]) * D + d];
-          const float4 wx = *reinterpret_cast<const float4 *>(q + 4), wy = *reinterpret_cast<const float4 *>(q + 8);
-          const float X[4] = {wx.x * dv, wx.y * dv, wx.z * dv, wx.w * dv};
-          const float Y[4] = {wy.x, wy.y, wy.z, wy.w};
-#pragma unroll
-          for (int cy = 0; cy < 4; ++cy)
-#pragma unroll
-            for (int cx = 0; cx < 4; ++cx) acc[cy * 4 + cx] += Y[cy] * X[cx];
+        if constexpr (GM) {
+          for (int e = 0; e < n_e; ++e) {           // entries in list order: fixed summation order per channel
+            const float *q = ent + e * kEntStride;
+            if (__float_as_int(q[1]) != mygrp) continue;
+            tile_fma(q, (float)dout[(size_t)__float_as_int(q[0]) * D + d], acc);
+          }
+        } else {
+          tile_accumulate<half_t>(ent, n_e, dout, (size_t)D, d, active_c, acc);
         }
         __syncthreads();
       }
@@ -1321,26 +1200,22 @@ SN_EXPORT int sn_psroi_pool_bwd(const void *dout, const void *data, const float 
                                 int d_data_f32, float *d_trans, int R, int B, int H, int W, int output_dim, int group_size,
                                 int pooled, int sample_per_part, float spatial_scale, float trans_std, int group_major, void *ws,
                                 sn_stream_t stream) {
-  SN_REQUIRE(dout && data && rois && d_data && ws && R > 0 && B > 0 && output_dim > 0 && group_size > 0 && pooled > 0 &&
-                 sample_per_part > 0, "sn_psroi_pool_bwd: bad arguments");
-  SN_REQUIRE(H < 65536 && W < 65536 && pooled * pooled <= 256 && sample_per_part <= kMaxS,
-             "sn_psroi_pool_bwd: H, W < 65536, pooled <= 16 and sample_per_part <= %d required", kMaxS);
-  SN_REQUIRE(!trans || d_trans, "sn_psroi_pool_bwd: d_trans required with trans");
+  if (const int e = roi_bwd_check("sn_psroi_pool_bwd", output_dim > 0 && group_size > 0, dout, data, rois, trans, d_data, d_trans, ws, R,
+                                  B, H, W, pooled, sample_per_part))
+    return e;
   const int C = output_dim * group_size * group_size;
   const long gz = (long)group_size * group_size * sn_div_up(output_dim, 256);
   SN_REQUIRE(gz <= 65535 && B <= 65535, "sn_psroi_pool_bwd: grid too large");
   hipStream_t s = sn_stream(stream);
   int4 *win = (int4 *)ws;
-  hipLaunchKernelGGL(dpsroi_window_kernel, dim3(sn_div_up(R, 4)), dim3(256), 0, s, rois, trans, win, R, H, W, pooled,
-                     sample_per_part, spatial_scale, trans_std);
-  SN_CHECK_LAUNCH();
+  if (const int e = roi_bwd_windows(rois, trans, win, R, H, W, pooled, sample_per_part, spatial_scale, trans_std, s)) return e;
   const int tiles = sn_div_up(W, 4) * sn_div_up(H, 4);
   if (group_major)
-    hipLaunchKernelGGL(psroi_ps_bwd_data_gm_kernel, dim3(tiles, B, (unsigned)sn_div_up(C, 256)), dim3(256), 0, s, (const half_t *)dout,
+    hipLaunchKernelGGL(psroi_ps_bwd_data_kernel<true>, dim3(tiles, B, (unsigned)sn_div_up(C, 256)), dim3(256), 0, s, (const half_t *)dout,
                        rois, trans, (const int4 *)win, d_data, d_data_f32, R, H, W, C, pooled, sample_per_part, group_size, output_dim,
                        spatial_scale, trans_std);
   else
-    hipLaunchKernelGGL(psroi_ps_bwd_data_kernel, dim3(tiles, B, (unsigned)gz), dim3(256), 0, s, (const half_t *)dout, rois, trans,
+    hipLaunchKernelGGL(psroi_ps_bwd_data_kernel<false>, dim3(tiles, B, (unsigned)gz), dim3(256), 0, s, (const half_t *)dout, rois, trans,
                        (const int4 *)win, d_data, d_data_f32, R, H, W, C, pooled, sample_per_part, group_size, output_dim,
                        spatial_scale, trans_std);
   SN_CHECK_LAUNCH();

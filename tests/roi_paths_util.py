@@ -175,7 +175,8 @@ ALL = CLASSES
 SMALL = ('none', '<=2', '3', '4')
 
 DPSROI_CASES = [
-    # generic kernels (pooled * pooled > 64): dpsroi_fwd_kernel, dpsroi_bwd_data_kernel (dynamic LDS), dpsroi_bwd_trans_kernel
+    # generic kernels (pooled * pooled > 64): dpsroi_fwd_kernel, dpsroi_bwd_data_kernel (dynamic LDS), dpsroi_bwd_trans_kernel (its
+    # window walk is also the oversized branch of dpsroi_bwd_trans_roi_kernel: trans_window_walk)
     PoolCase('generic-P14-mask-head', 2, 64, 20, 24, 24, 14, 4, SMALL),
     PoolCase('generic-P14-large-map', 1, 64, 72, 80, 8, 14, 4, ('none', '<=2', '3', '4', '5-8'), wh_max=700.0, big=True, dense=True),
     PoolCase('generic-P16-S2', 1, 64, 12, 12, 8, 16, 2, ('none', '<=2', '3'), dense=True),

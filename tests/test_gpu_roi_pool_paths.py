@@ -119,7 +119,8 @@ def test_dpsroi_pool_paths_vs_oracle(case):
 def test_position_sensitive_pool_paths_vs_oracle(case):
     """sn_psroi_pool_fwd / _bwd (G = P = 3) on a 40 x 44 map with RoIs of most of the map: the sample-loop branch of
     psroi_ps_bwd_trans_kernel (windows beyond 8 cells), the wave-per-bin forward (D = 40 >= 32) and the thread-per-element one
-    (D = 5) with large windows, S = 8; both channel orders."""
+    (D = 5) with large windows, S = 8; both channel orders (psroi_ps_bwd_data_kernel<false> / <true>: one template, built from
+    the RoI scan and bin weights the dpsroi_bwd_data kernels use)."""
     _pool_case(case)
 
 

@@ -65,3 +65,19 @@ def test_hot_kernels_keep_their_accumulators_in_registers():
     for name, res in roi.items():
         if 'dpsroi_bwd_data_mfma_kernel' in name:
             assert res['VGPRs'] <= 96 and res['Occupancy'] >= 5, res
+
+
+def test_tile_owner_data_gradients_keep_registers_and_occupancy():
+    """The four tile-owner data-gradient kernels of the RoI pooling are built from shared device functions (the RoI scan, the bin's
+    tile weights, the wave-order prefix): 16 accumulators per thread stay in registers, nothing spills, and the waves per SIMD are
+    those the kernels had as four separate copies."""
+    roi = _resources('roi_deform')
+    # mangled-name fragment -> waves per SIMD; ILb0E / ILb1E: the operator's channel order / group-major
+    want = {'22dpsroi_bwd_data_kernelP': 6, '27dpsroi_bwd_data_mfma_kernelP': 5, '24psroi_ps_bwd_data_kernelILb0EE': 6,
+            '24psroi_ps_bwd_data_kernelILb1EE': 8}
+    for frag, occ in want.items():
+        hits = {k: v for k, v in roi.items() if frag in k}
+        assert len(hits) == 1, (frag, sorted(roi))
+        for name, res in hits.items():
+            assert res['ScratchSize'] == 0 and res['VGPRs Spill'] == 0 and res['SGPRs Spill'] == 0, (name, res)
+            assert res['Occupancy'] >= occ, (name, res)
