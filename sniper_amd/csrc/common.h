@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/sniper_hip.h"
 
@@ -50,7 +51,35 @@ static inline hipStream_t sn_stream(sn_stream_t s) { return (hipStream_t)s; }
 static inline int sn_div_up(int a, int b) { return (a + b - 1) / b; }
 static inline size_t sn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// integer environment switch read once at load time (static initialisers of the A/B and tuning overrides)
+static inline int sn_env_int(const char *name, int dflt) {
+  const char *v = getenv(name);
+  return v && *v ? atoi(v) : dflt;
+}
+// output extent of a convolution / pooling window along one axis
+static inline int sn_conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
+// 1-D grid of a grid-stride kernel with 256-thread blocks: one thread per element up to `cap` blocks, never an empty grid
+static inline int sn_blocks(long total, int cap) {
+  const long b = (total + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 constexpr int kWave = 64;  // CDNA wavefront width
+
+typedef _Float16 half_t;
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+
+// order-preserving map float32 -> uint32 (any sign, no NaN): a < b <=> key(a) < key(b)
+__device__ __forceinline__ unsigned sn_float_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// dst[e] += sum_k part[k * n + e], e < n: per-block partial sums added in block order (no atomics, the same bits every run) --
+// the finish of the depthwise / grouped weight gradients and of the bias gradient (common.hip)
+int sn_partial_sum(const float *part, int nblk, long n, float *dst, hipStream_t s);
 
 // Division by a launch-invariant divisor as multiply-high + shift (n < 2^31, d >= 1): q = (umulhi(n, mul) + n) >> sh.  An integer
 // division costs ~40 VALU instructions on gfx950 (64-bit: ~80); index decompositions of element-wise kernels use these instead.

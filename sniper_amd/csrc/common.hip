@@ -1,4 +1,4 @@
-// common.hip -- error reporting + version for libsniper_hip.so
+// common.hip -- error reporting, version and the ordered sum of per-block partials for libsniper_hip.so
 #include "common.h"
 
 #include <stdarg.h>
@@ -49,6 +49,30 @@ struct DebugInit {
 }  // namespace
 
 int sn_debug_get(SnDebugOption which) { return g_debug[which].load(std::memory_order_relaxed); }
+
+__global__ __launch_bounds__(256) void partial_sum_kernel(const float *__restrict__ part, int nblk, long n, float *__restrict__ dst) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  // the blocks are added in block order (fixed bits), but their loads are independent: eight in flight instead of a chain
+  // of nblk dependent L2 round trips (13.5 us for 96 blocks)
+  float s = 0.f;
+  int k = 0;
+  for (; k + 8 <= nblk; k += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(k + u) * n + e];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; k < nblk; ++k) s += part[(size_t)k * n + e];
+  dst[e] += s;
+}
+
+int sn_partial_sum(const float *part, int nblk, long n, float *dst, hipStream_t s) {
+  hipLaunchKernelGGL(partial_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, nblk, n, dst);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
 
 SN_EXPORT int sn_debug_option(const char *name, int value) {
   SN_REQUIRE(name, "sn_debug_option: null name");

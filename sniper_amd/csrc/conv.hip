@@ -185,11 +185,7 @@ struct ConvPlan {
 // Tuning override (tools/conv_tune.py, tests): -1 = the built-in table, 0 = the register-staged kernel (conv_igemm_kernel) only,
 // else that LDS-DMA configuration (conv_dma_config) for every layer that qualifies.  Process-wide; not meant to change while
 // launches are in flight.
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-static std::atomic<int> g_conv_cfg{env_int("SNIPER_CONV_CFG", -1)};   // whole-program A/B (tools/ab.sh) without code changes
+static std::atomic<int> g_conv_cfg{sn_env_int("SNIPER_CONV_CFG", -1)};   // whole-program A/B (tools/ab.sh) without code changes
 SN_EXPORT int sn_conv_tune(int cfg) {
   SN_REQUIRE(cfg == -1 || cfg == 0 || conv_dma_config(cfg).bm > 0, "sn_conv_tune: no configuration %d", cfg);
   g_conv_cfg.store(cfg, std::memory_order_relaxed);
@@ -217,11 +213,9 @@ static int conv_dma_choice_balanced(int M, int Nout, int nk, bool dgrad) {
   return dgrad ? bal_d : bal;
 }
 
-static int conv_dma_choice(int M, int Nout, int nk, bool dgrad) { return conv_dma_choice_balanced(M, Nout, nk, dgrad); }
-
 // A/B and test switch: 0 = a stride-2 data gradient visits every tap for every destination pixel (three quarters of them
 // zero-filled), 1 (default) = by parity class (ConvParams::cls)
-static std::atomic<int> g_dgrad_by_class{env_int("SNIPER_DGRAD_BY_CLASS", 1)};
+static std::atomic<int> g_dgrad_by_class{sn_env_int("SNIPER_DGRAD_BY_CLASS", 1)};
 SN_EXPORT int sn_conv_dgrad_by_class(int on) {
   g_dgrad_by_class.store(on ? 1 : 0, std::memory_order_relaxed);
   return SN_OK;
@@ -244,7 +238,7 @@ static ConvPlan conv_plan(const ConvParams &p, bool dgrad, int use_cfg = -1) {
                           g_dgrad_by_class.load(std::memory_order_relaxed) != 0;
     const int nk_full = p.KH * p.KW * (p.Cin / 64);
     const int nk = by_class ? std::max(1, ((p.KH + 1) / 2) * ((p.KW + 1) / 2) * (p.Cin / 64)) : nk_full;    // the busiest class
-    int cfg = use_cfg > 0 ? use_cfg : (forced >= 0 ? forced : conv_dma_choice(p.M, p.Nout, nk, dgrad));
+    int cfg = use_cfg > 0 ? use_cfg : (forced >= 0 ? forced : conv_dma_choice_balanced(p.M, p.Nout, nk, dgrad));
     if (by_class && cfg == 18 && use_cfg <= 0 && forced < 0) cfg = 16;      // (the specialised kernel carries no class arithmetic: conv_dma.hip kClassOk)
     // the persistent twins (24 / 26) of the 160 x 128 configurations: launches of >= 4 whole tiles per CU that divide over the 512
     // resident workgroups, short contractions (what a tile pays outside its K loop is what the persistent loop overlaps)
@@ -301,8 +295,8 @@ static void conv_fwd_params(ConvParams &p, const void *x, const void *w, const f
                             int stride, int pad, int dil, int relu, int out_f32) {
   p.x = (const half_t *)x; p.w = (const half_t *)w; p.y = y; p.bias = bias; p.res = (const half_t *)residual;
   p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.in_ps = in_pix_stride;
-  p.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  p.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  p.Ho = sn_conv_out(H, KH, stride, pad, dil);
+  p.Wo = sn_conv_out(W, KW, stride, pad, dil);
   p.Nout = Cout; p.out_ps = out_pix_stride; p.res_ps = res_pix_stride;
   p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
   p.M = N * p.Ho * p.Wo; p.relu = relu; p.out_f32 = out_f32;
@@ -420,6 +414,23 @@ SN_EXPORT size_t sn_conv_fwd_splitk_workspace_bytes(int N, int H, int W, int Cin
   return sp.ksplit > 1 ? sn_align((size_t)sp.ksplit * sp.slab_elems * sizeof(float)) : 0;
 }
 
+// the split forward of p (sp.ksplit > 1, ws holds sp.ksplit slabs): fp32 partial tiles into ws, then the ordered reduce with p's epilogue
+// (and the second output y2, or null)
+static int conv_splitk_run(const ConvParams &p, const SplitPlan &sp, void *ws, int out_f32, half_t *y2, int y2_pix_stride,
+                           const float *y2_scale, const float *y2_shift, int y2_relu, hipStream_t s) {
+  ConvParams q = p;
+  q.y = ws; q.out_f32 = 1; q.out_ps = p.Nout; q.bias = nullptr; q.res = nullptr; q.res_ps = 0; q.relu = 0;
+  q.ksplit = sp.ksplit;
+  q.ksplit_stride = (long)sp.slab_elems;
+  if (int rc = conv_launch<false>(q, s, sp.cfg)) return rc;
+  const long total = (long)p.M * ((p.Nout + 7) / 8);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(sn_blocks(total, 4096)), dim3(256), 0, s, (const float *)ws, sp.ksplit, sp.slab_elems,
+                     (long)p.M, p.Nout, p.bias, p.res, p.res_ps, (half_t *)p.y, p.out_ps, p.relu, y2, y2_pix_stride, y2_scale, y2_shift,
+                     y2_relu, out_f32);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
 static int conv_fwd_splitk_impl(const char *who, int out_f32, const void *x, const void *w, const float *bias, const void *residual, void *y, int N, int H, int W,
                                  int Cin, int in_pix_stride, int Cout, int out_pix_stride, int res_pix_stride, int KH, int KW,
                                  int stride, int pad, int dil, int relu, void *ws, size_t ws_bytes, sn_stream_t stream) {
@@ -435,19 +446,7 @@ static int conv_fwd_splitk_impl(const char *who, int out_f32, const void *x, con
   SN_REQUIRE(ws && ws_bytes >= (size_t)sp.ksplit * sp.slab_elems * sizeof(float),
              "%s: %zu bytes of scratch needed (sn_conv_fwd_splitk_workspace_bytes), got %zu", who,
              (size_t)sp.ksplit * sp.slab_elems * sizeof(float), ws_bytes);
-  ConvParams q = p;
-  q.y = ws; q.out_f32 = 1; q.out_ps = p.Nout; q.bias = nullptr; q.res = nullptr; q.res_ps = 0; q.relu = 0;
-  q.ksplit = sp.ksplit;
-  q.ksplit_stride = (long)sp.slab_elems;
-  if (int rc = conv_launch<false>(q, sn_stream(stream), sp.cfg)) return rc;
-  const long total = (long)p.M * ((p.Nout + 7) / 8);
-  long blocks = (total + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, sn_stream(stream), (const float *)ws, sp.ksplit,
-                     sp.slab_elems, (long)p.M, p.Nout, bias, (const half_t *)residual, res_pix_stride, (half_t *)y, out_pix_stride, relu,
-                     (half_t *)nullptr, 0, (const float *)nullptr, (const float *)nullptr, 0, out_f32);
-  SN_CHECK_LAUNCH();
-  return SN_OK;
+  return conv_splitk_run(p, sp, ws, out_f32, nullptr, 0, nullptr, nullptr, 0, sn_stream(stream));
 }
 
 SN_EXPORT int sn_conv_fwd_splitk(const void *x, const void *w, const float *bias, const void *residual, void *y, int N, int H, int W,
@@ -498,21 +497,8 @@ SN_EXPORT int sn_conv_fwd_dual(const void *x, const void *w, const float *bias, 
   SN_REQUIRE(y2 && y2_scale && y2_shift && conv_dual_ok(p, y2_pix_stride),
              "sn_conv_fwd_dual: the layer does not take the 16-byte pipelined epilogue (query sn_conv_fwd_dual_ok)");
   const SplitPlan sp = conv_split_plan(p);
-  if (sp.ksplit > 1 && ws && ws_bytes >= (size_t)sp.ksplit * sp.slab_elems * sizeof(float)) {
-    ConvParams q = p;
-    q.y = ws; q.out_f32 = 1; q.out_ps = p.Nout; q.bias = nullptr; q.res = nullptr; q.res_ps = 0; q.relu = 0;
-    q.ksplit = sp.ksplit;
-    q.ksplit_stride = (long)sp.slab_elems;
-    if (int rc = conv_launch<false>(q, sn_stream(stream), sp.cfg)) return rc;
-    const long total = (long)p.M * (p.Nout / 8);
-    long blocks = (total + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, sn_stream(stream), (const float *)ws, sp.ksplit,
-                       sp.slab_elems, (long)p.M, p.Nout, bias, (const half_t *)residual, res_pix_stride, (half_t *)y, out_pix_stride, relu,
-                       (half_t *)y2, y2_pix_stride, y2_scale, y2_shift, y2_relu, 0);
-    SN_CHECK_LAUNCH();
-    return SN_OK;
-  }
+  if (sp.ksplit > 1 && ws && ws_bytes >= (size_t)sp.ksplit * sp.slab_elems * sizeof(float))
+    return conv_splitk_run(p, sp, ws, 0, (half_t *)y2, y2_pix_stride, y2_scale, y2_shift, y2_relu, sn_stream(stream));
   p.out2 = (half_t *)y2; p.out2_ps = y2_pix_stride; p.o2_scale = y2_scale; p.o2_shift = y2_shift; p.o2_relu = y2_relu;
   return conv_launch<false>(p, sn_stream(stream));
 }
@@ -570,7 +556,7 @@ SN_EXPORT int sn_conv_stem_fwd(const void *xp, const void *w, const float *bias,
 static void conv_dgrad_params(ConvParams &p, const void *dy, const void *wt, const void *accumulate, void *dx, int N, int H, int W,
                               int Cin, int dx_pix_stride, int Cout, int dy_pix_stride, int acc_pix_stride, int KH, int KW, int stride,
                               int pad, int dil, int out_f32) {
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Ho = sn_conv_out(H, KH, stride, pad, dil), Wo = sn_conv_out(W, KW, stride, pad, dil);
   p.x = (const half_t *)dy; p.w = (const half_t *)wt; p.y = dx; p.bias = nullptr; p.res = (const half_t *)accumulate;
   p.N = N; p.H = Ho; p.W = Wo; p.Cin = Cout; p.in_ps = dy_pix_stride;
   p.Ho = H; p.Wo = W; p.Nout = Cin; p.out_ps = dx_pix_stride; p.res_ps = acc_pix_stride;
@@ -744,8 +730,8 @@ struct WgradPlan {
 
 static WgradPlan wgrad_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil) {
   WgradPlan q;
-  q.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  q.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  q.Ho = sn_conv_out(H, KH, stride, pad, dil);
+  q.Wo = sn_conv_out(W, KW, stride, pad, dil);
   q.taps = KH * KW;
   q.gx = sn_div_up(Cout, 128);
   q.gy = sn_div_up(Cin, 128);
@@ -790,10 +776,7 @@ static int wgrad_legacy(const void *dy, const void *x, float *dw, int N, int H, 
   hipLaunchKernelGGL(conv_wgrad_kernel, dim3(wgrad_grid(p, q.gx, q.gy, q.taps * q.splits)), dim3(256), 0, s, p);
   SN_CHECK_LAUNCH();
   if (p.slab) {
-    long blocks = (long)((n / 4 + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float *)p.slab, q.splits, n, dw);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(sn_blocks((long)(n / 4), 4096)), dim3(256), 0, s, (const float *)p.slab, q.splits, n, dw);
     SN_CHECK_LAUNCH();
   }
   return SN_OK;
@@ -828,8 +811,8 @@ static bool wgrad_desc_params(const sn_wgrad_desc &d, WgradParams &p) {
   p.N = d.N; p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.Cout = d.Cout; p.dy_ps = d.dy_pix_stride; p.x_ps = d.x_pix_stride;
   p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad = d.pad; p.dil = d.dil;
   if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.KH <= 0 || d.KW <= 0 || d.stride <= 0 || d.dil <= 0) return false;
-  p.Ho = (d.H + 2 * d.pad - d.dil * (d.KH - 1) - 1) / d.stride + 1;
-  p.Wo = (d.W + 2 * d.pad - d.dil * (d.KW - 1) - 1) / d.stride + 1;
+  p.Ho = sn_conv_out(d.H, d.KH, d.stride, d.pad, d.dil);
+  p.Wo = sn_conv_out(d.W, d.KW, d.stride, d.pad, d.dil);
   p.slab = nullptr; p.slab_stride = 0; p.units_per_split = 0;
   return p.Ho > 0 && p.Wo > 0;
 }

@@ -4,11 +4,6 @@
 #include <atomic>
 #include "common.h"
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 struct ConvParams {
   const half_t *x;  // source activations
   const half_t *w;  // [Nout][taps][Cin] fp16
@@ -56,19 +51,38 @@ struct ConvParams {
 };
 
 
-static inline void conv_fastdiv_make(unsigned d, unsigned &mul, unsigned &sh) {
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  mul = (unsigned)((((unsigned long long)1 << 32) * (((unsigned long long)1 << s) - d)) / d + 1);
-  sh = s;
-}
 static inline void conv_fastdiv_fill(ConvParams &p) {
   p.rows_img = p.cls ? (p.Ho / 2) * (p.Wo / 2) : p.Ho * p.Wo;
   p.row_len = p.cls ? p.Wo / 2 : p.Wo;
-  conv_fastdiv_make((unsigned)p.rows_img, p.fda_mul, p.fda_sh);
-  conv_fastdiv_make((unsigned)p.row_len, p.fdb_mul, p.fdb_sh);
+  const SnDiv a = sn_div_make((unsigned)p.rows_img), b = sn_div_make((unsigned)p.row_len);
+  p.fda_mul = a.mul; p.fda_sh = a.sh;
+  p.fdb_mul = b.mul; p.fdb_sh = b.sh;
 }
-__device__ __forceinline__ int conv_fastdiv(int n, unsigned mul, unsigned sh) { return (int)((__umulhi((unsigned)n, mul) + (unsigned)n) >> sh); }
+
+// ---- LDS-DMA and transposing-read primitives of the pipelined kernels (conv_dma.hip, conv_wgrad_ps.hip, gconv.hip)
+typedef __attribute__((address_space(3))) void *lds_ptr_t;
+typedef short short4v __attribute__((vector_size(8)));
+
+// 64 lanes x 16 B: lane l's bytes land at dst + 16 l (dst wave-uniform).  Kept out of the kernel templates: the host pass
+// rejects the address-space cast, and an error inside a __global__ template silently drops its host stub.
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, half_t *dst, unsigned voff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// One 8-deep MFMA fragment with k = pixel from an LDS image stored as it lies in memory ([pixel][channel]): two transposing reads,
+// `second` halfs apart.  Per 16-lane group (one value of lane >> 4) ds_read_b64_tr_b16 takes a block of 4 rows x 16 columns -- lane
+// 4a + b of the group supplies the address of row a, columns 4b .. 4b + 3 -- and hands lane i column i of the four rows.  EXEC must be
+// all ones here.
+__device__ __forceinline__ half8 tr_frag(const half_t *img, int off, int second) {
+  typedef __attribute__((address_space(3))) short4v *lds_v4;
+  union { short4v s[2]; half8 h; } u;
+  u.s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(img + off));
+  u.s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(img + off + second));
+  return u.h;
+}
 
 // LDS-DMA pipelined implicit-GEMM kernels (conv_dma.hip).  cfg: see conv_dma_config().
 struct ConvDmaConfig { int bm, bn, threads, stages, lds_bytes; };

@@ -23,14 +23,6 @@
 #include "conv_common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-
-// 64 lanes x 16 B: lane l's bytes land at dst + 16 l (dst wave-uniform).  Kept out of the kernel template: the host pass
-// rejects the address-space cast, and an error inside a __global__ template silently drops its host stub.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, half_t *dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
-}
-
 // sum over the 16 lanes of a DPP row (the lanes that share lane >> 4), result in every lane: four VALU adds with DPP operands
 // (quad_perm xor 1, xor 2, row_half_mirror, row_mirror) instead of four ds_bpermute round trips per value
 template <int CTRL>
@@ -68,11 +60,6 @@ __device__ __forceinline__ void tie(half8 &x) {
   x = __builtin_bit_cast(half8, v);
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // PS ("producer / consumer specialised", round 3): the workgroup has WMW x WNW CONSUMER waves (one per SIMD for 2 x 2) that only read
 // fragments and multiply, plus four PRODUCER waves (the second wave of each SIMD) that only compute gather addresses and issue the
 // LDS-DMA pieces, S - 1 stages ahead.  A wave's instruction stream is in order, so in the unspecialised kernel a K-step costs
@@ -87,7 +74,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 // register group right after the epilogue consumed it), so the fill that every workgroup of the one-tile-per-workgroup launch pays
 // in front of its first MFMA (profiles/r05_conv_trace_s3.txt: 8 of a workgroup's 28 thousand cycles on the 4-K-step layers, more
 // with a cold residual) is paid once per workgroup instead of once per tile.  Taken for launches of >= 4 tiles per CU whose tile
-// count divides over the 512 resident workgroups (conv_dma_choice: the stage-3 expansions forward, the reductions' data gradients,
+// count divides over the 512 resident workgroups (conv_dma_choice_balanced: the stage-3 expansions forward, the reductions' data gradients,
 // stages 2 and 4).  The statistics scratch sits behind the ring (the ring is live while a tile's statistics are reduced).
 template <bool DGRAD, int BM, int BN, int WMW, int WNW, int S, int MINW, bool PS = false, bool PERSIST = false>
 __global__ __launch_bounds__(64 * (WMW * WNW + (PS ? 4 : 0)), MINW) void conv_dma_kernel(const ConvParams p, int mtiles, int ntiles) {
@@ -157,9 +144,9 @@ __global__ __launch_bounds__(64 * (WMW * WNW + (PS ? 4 : 0)), MINW) void conv_dm
   const int Mrows = by_class ? p.cls_mc : p.M;
   // GEMM row -> destination (image, y, x) and flat pixel index, by multiplication (ConvParams::fda / fdb)
   auto row_decompose = [&](int m, int &img, int &oy, int &ox) {
-    img = conv_fastdiv(m, p.fda_mul, p.fda_sh);
+    img = (int)sn_div((unsigned)m, SnDiv{p.fda_mul, p.fda_sh, (unsigned)p.rows_img});
     const int rem = m - img * p.rows_img;
-    oy = conv_fastdiv(rem, p.fdb_mul, p.fdb_sh);
+    oy = (int)sn_div((unsigned)rem, SnDiv{p.fdb_mul, p.fdb_sh, (unsigned)p.row_len});
     ox = rem - oy * p.row_len;
     if (by_class) { oy = 2 * oy + cls_ph; ox = 2 * ox + cls_pw; }
   };

@@ -31,30 +31,9 @@
 #include "conv_common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef short short4v __attribute__((vector_size(8)));
-
 namespace {
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, half_t *dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
-}
-
-// one 8-deep MFMA fragment = two transposing reads, 16 tile rows apart
-__device__ __forceinline__ half8 tr_frag(const half_t *lds_tile, int off) {
-  typedef __attribute__((address_space(3))) short4v *lds_v4;
-  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_tile + off));
-  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_tile + off + 16 * 128));
-  union { short4v s[2]; half8 h; } u;
-  u.s[0] = lo;
-  u.s[1] = hi;
-  return u.h;
-}
+constexpr int kTrSecond = 16 * 128;   // tr_frag: the two transposing reads of a fragment are 16 tile rows (of 128 channels) apart
 
 // a lane whose channel chunk lies beyond Cout / Cin carries this voffset: with every tensor < 1 GB (checked on the host) no step
 // offset can bring it back under a descriptor's num_records, so it reads zeros for the whole job without a select per piece
@@ -206,9 +185,9 @@ __global__ __launch_bounds__(64 * (16 * NA / MI + 4)) void wgrad_ps_kernel(const
   auto read = [&](int buf, int ks, half8 (&fa)[MI], half8 (&fb)[NI]) {
     const half_t *const sa = lds + buf * kStage + ks * 32 * 128, *const sb = sa + NA * kTile;
 #pragma unroll
-    for (int i = 0; i < MI; ++i) fa[i] = tr_frag(sa, a_off[i]);
+    for (int i = 0; i < MI; ++i) fa[i] = tr_frag(sa, a_off[i], kTrSecond);
 #pragma unroll
-    for (int jn = 0; jn < NI; ++jn) fb[jn] = tr_frag(sb, b_off[jn]);
+    for (int jn = 0; jn < NI; ++jn) fb[jn] = tr_frag(sb, b_off[jn], kTrSecond);
   };
   auto mma = [&](const half8 (&fa)[MI], const half8 (&fb)[NI]) {
 #pragma unroll

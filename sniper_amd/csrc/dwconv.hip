@@ -8,9 +8,6 @@
 // contiguous 144-byte run.
 #include "common.h"
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int kT = 9;  // 3x3
 
 __device__ __forceinline__ void load_w(const half_t *__restrict__ w, int ch, float wf[8][kT]) {
@@ -105,7 +102,7 @@ __global__ __launch_bounds__(256) void dwconv_dgrad_kernel(const half_t *__restr
 
 // dw[c][tap] += sum_pix dy[pix][c] * x[src(pix, tap)][c].  A thread owns 8 channels for its whole life (72 fp32
 // accumulators) and walks output pixels; the block folds its row lanes through LDS in lane order and writes ONE partial
-// per (channel, tap) to its slab [pixel block][C][9]; dwconv_wgrad_finish_kernel adds the slabs to dw in block order.
+// per (channel, tap) to its slab [pixel block][C][9]; sn_partial_sum adds the slabs to dw in block order.
 // No atomics anywhere: the same bits every run (the previous version folded with ds_add_f32 + global atomics).
 constexpr int kDwChunks = 32;  // 8-channel chunks per block (256 channels): LDS rpp * cb * 72 * 4 B <= 72 KB
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const half_t *__restrict__ dy, const half_t *__restrict__ x,
@@ -163,31 +160,23 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const half_t *__restr
   }
 }
 
-__global__ __launch_bounds__(256) void dwconv_wgrad_finish_kernel(const float *__restrict__ part, int nblk, long n, float *__restrict__ dw) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < nblk; ++k) s += part[(size_t)k * n + e];
-  dw[e] += s;
-}
-
+// argument check shared by the entry points; -> the output extent (Ho, Wo)
 static int dw_check(const void *a, const void *b, const void *c, int N, int H, int W, int C, int KH, int KW, int stride, int pad,
-                    int dil, const char *who) {
+                    int dil, int ps_a, int ps_b, const char *who, int *Ho, int *Wo) {
   SN_REQUIRE(a && b && c && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "%s: bad arguments (C %% 8 == 0 required)", who);
   SN_REQUIRE(KH == 3 && KW == 3, "%s: only the 3x3 depthwise kernel is built (MobileNetV2)", who);
   SN_REQUIRE(stride > 0 && dil > 0 && pad >= 0, "%s: bad geometry", who);
+  *Ho = sn_conv_out(H, KH, stride, pad, dil);
+  *Wo = sn_conv_out(W, KW, stride, pad, dil);
+  SN_REQUIRE(*Ho > 0 && *Wo > 0 && ps_a % 8 == 0 && ps_b % 8 == 0, "%s: bad strides", who);
   return SN_OK;
 }
-static int dw_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+static int dw_blocks(long total) { return sn_blocks(total, 16384); }
 
 SN_EXPORT int sn_dwconv_fwd(const void *x, const void *w, void *y, int N, int H, int W, int C, int in_pix_stride,
                             int out_pix_stride, int KH, int KW, int stride, int pad, int dil, sn_stream_t stream) {
-  if (int rc = dw_check(x, w, y, N, H, W, C, KH, KW, stride, pad, dil, "sn_dwconv_fwd")) return rc;
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  SN_REQUIRE(Ho > 0 && Wo > 0 && in_pix_stride % 8 == 0 && out_pix_stride % 8 == 0, "sn_dwconv_fwd: bad strides");
+  int Ho, Wo;
+  if (int rc = dw_check(x, w, y, N, H, W, C, KH, KW, stride, pad, dil, in_pix_stride, out_pix_stride, "sn_dwconv_fwd", &Ho, &Wo)) return rc;
   hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(dw_blocks((long)N * Ho * Wo * (C / 8))), dim3(256), 0, sn_stream(stream),
                      (const half_t *)x, (const half_t *)w, (half_t *)y, N, H, W, C, in_pix_stride, out_pix_stride, Ho, Wo, stride,
                      pad, dil);
@@ -198,9 +187,8 @@ SN_EXPORT int sn_dwconv_fwd(const void *x, const void *w, void *y, int N, int H,
 SN_EXPORT int sn_dwconv_dgrad(const void *dy, const void *w, const void *accumulate, void *dx, int N, int H, int W, int C,
                               int dy_pix_stride, int acc_pix_stride, int dx_pix_stride, int KH, int KW, int stride, int pad,
                               int dil, sn_stream_t stream) {
-  if (int rc = dw_check(dy, w, dx, N, H, W, C, KH, KW, stride, pad, dil, "sn_dwconv_dgrad")) return rc;
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  SN_REQUIRE(Ho > 0 && Wo > 0 && dy_pix_stride % 8 == 0 && dx_pix_stride % 8 == 0, "sn_dwconv_dgrad: bad strides");
+  int Ho, Wo;
+  if (int rc = dw_check(dy, w, dx, N, H, W, C, KH, KW, stride, pad, dil, dy_pix_stride, dx_pix_stride, "sn_dwconv_dgrad", &Ho, &Wo)) return rc;
   hipLaunchKernelGGL(dwconv_dgrad_kernel, dim3(dw_blocks((long)N * H * W * (C / 8))), dim3(256), 0, sn_stream(stream),
                      (const half_t *)dy, (const half_t *)w, (const half_t *)accumulate, (half_t *)dx, N, H, W, C, dy_pix_stride,
                      acc_pix_stride, dx_pix_stride, Ho, Wo, stride, pad, dil);
@@ -219,7 +207,7 @@ static int dw_wgrad_blocks(long M, int C, int *pix_per_block) {
 
 SN_EXPORT size_t sn_dwconv_wgrad_workspace_bytes(int N, int H, int W, int C, int KH, int KW, int stride, int pad, int dil) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return 0;
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Ho = sn_conv_out(H, KH, stride, pad, dil), Wo = sn_conv_out(W, KW, stride, pad, dil);
   if (Ho <= 0 || Wo <= 0) return 0;
   int ppb;
   return sn_align(sizeof(float) * (size_t)dw_wgrad_blocks((long)N * Ho * Wo, C, &ppb) * C * kT);
@@ -228,9 +216,8 @@ SN_EXPORT size_t sn_dwconv_wgrad_workspace_bytes(int N, int H, int W, int C, int
 SN_EXPORT int sn_dwconv_wgrad(const void *dy, const void *x, float *dw, int N, int H, int W, int C, int dy_pix_stride,
                               int x_pix_stride, int KH, int KW, int stride, int pad, int dil, void *ws, size_t ws_bytes,
                               sn_stream_t stream) {
-  if (int rc = dw_check(dy, x, dw, N, H, W, C, KH, KW, stride, pad, dil, "sn_dwconv_wgrad")) return rc;
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  SN_REQUIRE(Ho > 0 && Wo > 0 && dy_pix_stride % 8 == 0 && x_pix_stride % 8 == 0, "sn_dwconv_wgrad: bad strides");
+  int Ho, Wo;
+  if (int rc = dw_check(dy, x, dw, N, H, W, C, KH, KW, stride, pad, dil, dy_pix_stride, x_pix_stride, "sn_dwconv_wgrad", &Ho, &Wo)) return rc;
   const long M = (long)N * Ho * Wo;
   int ppb;
   const int blocks = dw_wgrad_blocks(M, C, &ppb);
@@ -240,10 +227,7 @@ SN_EXPORT int sn_dwconv_wgrad(const void *dy, const void *x, float *dw, int N, i
   hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((unsigned)blocks, sn_div_up(C / 8, kDwChunks)), dim3(256), 0, s, (const half_t *)dy,
                      (const half_t *)x, (float *)ws, N, H, W, C, dy_pix_stride, x_pix_stride, Ho, Wo, stride, pad, dil, ppb);
   SN_CHECK_LAUNCH();
-  const long n = (long)C * kT;
-  hipLaunchKernelGGL(dwconv_wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float *)ws, blocks, n, dw);
-  SN_CHECK_LAUNCH();
-  return SN_OK;
+  return sn_partial_sum((const float *)ws, blocks, (long)C * kT, dw, s);
 }
 
 // ---------------------------------------------------------------------------------------------

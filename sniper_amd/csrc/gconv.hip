@@ -12,12 +12,9 @@
 // with the slab's weights transposed in registers and the taps gathered per dx pixel on the stride lattice.
 // The weight gradient contracts over pixels: dy and the tap-shifted x of 32 pixels go through a wave-private LDS image as they lie
 // ([pixel][channel], 16-byte writes), are read back transposed (ds_read_b64_tr_b16), and every workgroup writes ONE partial per weight to its slab of the
-// workspace; a finish kernel adds the slabs to dw in block order (no atomics: the same bits every run).
+// workspace; sn_partial_sum (common.hip) adds the slabs to dw in block order (no atomics: the same bits every run).
 // Everything else (Cg != Og, other widths, other kernel sizes, fp32 output) takes the plain kernels at the end of the file.
-#include "common.h"
 #include "conv_common.h"
-
-typedef _Float16 half_t;
 
 struct GconvParams {
   int N, H, W, Ho, Wo;        // input and output extents of the CONVOLUTION (the data gradient reads Ho x Wo, writes H x W)
@@ -118,18 +115,9 @@ __global__ __launch_bounds__(256) void gconv_mfma_kernel(const half_t *__restric
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int kTP = 40;       // halfs per row of a [32 pixels][32 channels] LDS image (80 B: 16-byte aligned rows)
 
-// One MFMA fragment with k = pixel from an image stored as it lies in memory ([pixel][channel]): two transposing reads.  Per 16-lane
-// group (one value of lane >> 4) ds_read_b64_tr_b16 takes a block of 4 rows x 16 columns -- lane 4a + b of the group supplies the
-// address of row a, columns 4b .. 4b + 3 -- and hands lane i column i of the four rows.  Rows = pixels 8q + {0..3} and 8q + {4..7},
-// columns = the 16 channels of a block: lane (r, q) receives channel r of pixels 8q .. 8q + 7.  EXEC must be all ones here.
-typedef short gc_short4 __attribute__((vector_size(8)));
-__device__ __forceinline__ half8 gc_tr_frag(const half_t *img, int off) {
-  typedef __attribute__((address_space(3))) gc_short4 *lds_v4;
-  union { gc_short4 s[2]; half8 h; } u;
-  u.s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(img + off));
-  u.s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(img + off + 4 * kTP));
-  return u.h;
-}
+// tr_frag (conv_common.h) on these images: rows = pixels 8q + {0..3} and 8q + {4..7} -- the second read is 4 rows down -- columns =
+// the 16 channels of a block: lane (r, q) receives channel r of pixels 8q .. 8q + 7.
+constexpr int kTrSecond = 4 * kTP;
 
 // NB = 1: Cg <= 16, only the two diagonal 16 x 16 blocks of a slab hold weights;  NB = 2: Cg == 32, all four
 template <int T, int NB>
@@ -141,7 +129,7 @@ __global__ __launch_bounds__(256) void gconv_wgrad_mfma_kernel(const half_t *__r
   const int slab = blockIdx.y * (blockDim.x >> 6) + wave;
   const int ch0 = slab * 32;
   half_t *dyT = lds[wave][0];
-  const int tr_off = (8 * q + (r >> 2)) * kTP + 4 * (r & 3);      // gc_tr_frag: this lane's address of pixel row 8q + (r >> 2)
+  const int tr_off = (8 * q + (r >> 2)) * kTP + 4 * (r & 3);      // tr_frag: this lane's address of pixel row 8q + (r >> 2)
   floatx4 acc[T][2][NB];
 #pragma unroll
   for (int t = 0; t < T; ++t)
@@ -197,11 +185,11 @@ __global__ __launch_bounds__(256) void gconv_wgrad_mfma_kernel(const half_t *__r
       __syncthreads();
       if (t == 0) {
 #pragma unroll
-        for (int bo = 0; bo < 2; ++bo) fa[bo] = gc_tr_frag(dyT, tr_off + bo * 16);
+        for (int bo = 0; bo < 2; ++bo) fa[bo] = tr_frag(dyT, tr_off + bo * 16, kTrSecond);
       }
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi) {
-        const half8 fb = gc_tr_frag(xT, tr_off + bi * 16);
+        const half8 fb = tr_frag(xT, tr_off + bi * 16, kTrSecond);
         if (NB == 2) {
 #pragma unroll
           for (int bo = 0; bo < 2; ++bo) acc[t][bo][bi % NB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[bo], fb, acc[t][bo][bi % NB], 0, 0, 0);
@@ -228,14 +216,6 @@ __global__ __launch_bounds__(256) void gconv_wgrad_mfma_kernel(const half_t *__r
           if (o / p.Cg == ci / p.Cg) po[((size_t)(ch0 + o) * T + t) * p.Cg + ci % p.Cg] = acc[t][bo][i][e];
         }
       }
-}
-
-__global__ __launch_bounds__(256) void gconv_wgrad_finish_kernel(const float *__restrict__ part, int nblk, long n, float *__restrict__ dw) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < nblk; ++k) s += part[(size_t)k * n + e];
-  dw[e] += s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -329,6 +309,18 @@ __global__ __launch_bounds__(256) void gconv_plain_wgrad_kernel(const half_t *__
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------
+// the geometry of a problem whose arguments are in range; false = empty output
+static bool gc_geometry(GconvParams *p, int N, int H, int W, int C, int O, int groups, int KH, int KW, int stride, int pad, int dil) {
+  p->N = N; p->H = H; p->W = W; p->C = C; p->O = O; p->groups = groups;
+  p->Cg = C / groups; p->Og = O / groups;
+  p->KH = KH; p->KW = KW; p->stride = stride; p->pad = pad; p->dil = dil;
+  p->Ho = sn_conv_out(H, KH, stride, pad, dil);
+  p->Wo = sn_conv_out(W, KW, stride, pad, dil);
+  p->relu = 0; p->acc_ps = 0; p->cg_shift = p->s_shift = 0;
+  while ((1 << p->cg_shift) < p->Cg) ++p->cg_shift;
+  while ((1 << p->s_shift) < stride) ++p->s_shift;
+  return p->Ho > 0 && p->Wo > 0;
+}
 static int gc_check(const void *a, const void *b, const void *c, int N, int H, int W, int C, int O, int groups, int KH, int KW,
                     int stride, int pad, int dil, GconvParams *p, const char *who) {
   SN_REQUIRE(a && b && c, "%s: null pointer", who);
@@ -336,15 +328,7 @@ static int gc_check(const void *a, const void *b, const void *c, int N, int H, i
   SN_REQUIRE(groups > 1, "%s: groups == %d is a dense convolution (sn_conv_fwd / _dgrad / _wgrad)", who, groups);
   SN_REQUIRE(C % groups == 0 && O % groups == 0, "%s: C = %d and O = %d must be multiples of groups = %d", who, C, O, groups);
   SN_REQUIRE(!(groups == C && groups == O), "%s: groups == C == O is the depthwise convolution (sn_dwconv_*)", who);
-  p->N = N; p->H = H; p->W = W; p->C = C; p->O = O; p->groups = groups;
-  p->Cg = C / groups; p->Og = O / groups;
-  p->KH = KH; p->KW = KW; p->stride = stride; p->pad = pad; p->dil = dil;
-  p->Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  p->Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  SN_REQUIRE(p->Ho > 0 && p->Wo > 0, "%s: empty output", who);
-  p->relu = 0; p->acc_ps = 0; p->cg_shift = p->s_shift = 0;
-  while ((1 << p->cg_shift) < p->Cg) ++p->cg_shift;
-  while ((1 << p->s_shift) < stride) ++p->s_shift;
+  SN_REQUIRE(gc_geometry(p, N, H, W, C, O, groups, KH, KW, stride, pad, dil), "%s: empty output", who);
   SN_REQUIRE((long)N * H * W < (1l << 31) / 16 && (long)N * p->Ho * p->Wo < (1l << 31) / 16, "%s: too many pixels", who);
   return SN_OK;
 }
@@ -356,10 +340,7 @@ static bool gc_fast(const GconvParams &p) {
 }
 // waves per workgroup: every wave of a workgroup owns a slab that exists
 static int gc_waves(int nslab) { return nslab % 4 == 0 ? 4 : (nslab % 2 == 0 ? 2 : 1); }
-static int gc_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+static int gc_blocks(long total) { return sn_blocks(total, 16384); }
 
 template <bool DGRAD>
 static void gc_launch_mfma(const void *src, const void *w, const float *bias, const void *acc, void *dst, GconvParams &p, hipStream_t s) {
@@ -437,10 +418,7 @@ SN_EXPORT size_t sn_gconv_wgrad_workspace_bytes(int N, int H, int W, int C, int 
       dil <= 0 || pad < 0)
     return 0;
   GconvParams p;
-  p.N = N; p.H = H; p.W = W; p.C = C; p.O = O; p.groups = groups; p.Cg = C / groups; p.Og = O / groups; p.KH = KH; p.KW = KW; p.stride = stride;
-  p.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  p.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  if (p.Ho <= 0 || p.Wo <= 0) return 0;
+  if (!gc_geometry(&p, N, H, W, C, O, groups, KH, KW, stride, pad, dil)) return 0;
   int per;
   return sn_align(sizeof(float) * (size_t)gc_wgrad_blocks(p, &per) * O * KH * KW * p.Cg);
 }
@@ -477,7 +455,5 @@ SN_EXPORT int sn_gconv_wgrad(const void *dy, const void *x, float *dw, int N, in
                        (const half_t *)dy, (const half_t *)x, (float *)ws, p, per);
   }
   SN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gconv_wgrad_finish_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, (const float *)ws, blocks, nw, dw);
-  SN_CHECK_LAUNCH();
-  return SN_OK;
+  return sn_partial_sum((const float *)ws, blocks, nw, dw, s);
 }

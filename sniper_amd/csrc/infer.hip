@@ -304,11 +304,6 @@ SN_EXPORT int sn_aggregate_scatter(const void *d_parts, int P, int nc, const int
 
 // rows (total, 5) f32, problems q = image * nc + class at off[q] .. off[q] + count[q] (count: survivors of the NMS, a prefix of the
 // problem's segment).  In place: count[q] shrinks, the kept rows move to the front of the segment in order.
-__device__ __forceinline__ unsigned score_key(float s) {            // order-preserving map float32 -> uint32 (any sign, no NaN)
-  const unsigned u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void det_cap_kernel(float *__restrict__ rows, const int32_t *__restrict__ off,
                                                       int32_t *__restrict__ count, int nc, int max_per_image) {
   __shared__ int hist[256];
@@ -333,7 +328,7 @@ __global__ __launch_bounds__(256) void det_cap_kernel(float *__restrict__ rows, 
       const float *seg = rows + (size_t)off[q0 + j] * 5;
       const int n = count[q0 + j];
       for (int r = tid; r < n; r += 256) {
-        const unsigned k = score_key(seg[(size_t)r * 5 + 4]);
+        const unsigned k = sn_float_key(seg[(size_t)r * 5 + 4]);
         if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1);
       }
     }
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(256) void det_cap_kernel(float *__restrict__ rows, 
       if (r < n) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] = seg[(size_t)r * 5 + k];
-        keep = score_key(v[4]) >= thresh;
+        keep = sn_float_key(v[4]) >= thresh;
       }
       const unsigned long long m = __ballot(keep);
       if (keep) {

@@ -6,8 +6,6 @@
 //   pick             one channel per RoI (its class's negative / positive mask map) and the scatter back
 #include "common.h"
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------
 // MaskRcnnTarget.  rois (N,5) [b,x1,y1,x2,y2] in chip pixels, N = B * rois_per_image; mask_polys (B, max_gts, max_len):

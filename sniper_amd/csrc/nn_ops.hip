@@ -9,9 +9,6 @@
 #include "common.h"
 #include <algorithm>
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 // ---------------------------------------------------------------------------------------------
 // Stem input: NCHW fp32 image batch -> zero-padded NHWC4 fp16, with the bn_data affine folded in
 // (resnet_mx_101_e2e.py:402, use_global_stats, fix_gamma).  The 7x7/2 conv0 then runs on the
@@ -45,8 +42,7 @@ SN_EXPORT int sn_pack_stem_input(const float *x_nchw, void *out, int N, int C, i
   SN_REQUIRE(x_nchw && out && N > 0 && C >= 1 && C <= 4 && Hp >= H + pad_t && Wp >= W + pad_l,
              "sn_pack_stem_input: bad arguments");
   const long total = (long)N * Hp * Wp;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(pack_stem_kernel, dim3(blocks), dim3(256), 0, sn_stream(stream), x_nchw, (half_t *)out, N, C, H, W,
+  hipLaunchKernelGGL(pack_stem_kernel, dim3(sn_blocks(total, 4096)), dim3(256), 0, sn_stream(stream), x_nchw, (half_t *)out, N, C, H, W,
                      Hp, Wp, pad_t, pad_l, scale, shift);
   SN_CHECK_LAUNCH();
   return SN_OK;
@@ -405,10 +401,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(const half_t *__r
 }
 
 static int bn_shape_ok(int C) { return C >= 8 && C % 8 == 0; }
-static int ew_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+static int ew_blocks(long total) { return sn_blocks(total, 8192); }
 // grid of the row-walking BN kernels: x = row blocks (>= kBnUnroll*2 rows per thread, at most `cap`), y = 256-chunk slabs
 static dim3 bn_grid(int M, int C, int cap, int *rows_per_block) {
   const int cpr = C / 8, cb = cpr < kBnThreads ? cpr : kBnThreads, rpp = kBnThreads / cb;
@@ -495,45 +488,11 @@ SN_EXPORT int sn_bn_apply_blocks(const float *partials, int nblk, const void *x,
   return sn_bn_apply(x, y, M, C, ps_in, ps_out, scale, shift, relu, stream);
 }
 
-// Backward of y = relu?(BN_train(x)).  dgamma/dbeta (fp32, length C) are ACCUMULATED into (+=, the optimizer's
-// gradient arena is zeroed once per step); ws = sn_bn_workspace_bytes(M, C).  Three launches, no atomics, no memset:
-// partial reduce -> finalize -> dx.
-SN_EXPORT int sn_bn_backward(const void *dy, const void *x, const void *accumulate, void *dx, int M, int C, int ps_dy,
-                             int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean,
-                             const float *invstd, int relu, void *ws, float *dgamma, float *dbeta, sn_stream_t stream) {
-  SN_REQUIRE(dy && x && scale && shift && mean && invstd && ws && bn_shape_ok(C) && M > 0,
-             "sn_bn_backward: bad arguments (C=%d)", C);
-  hipStream_t s = sn_stream(stream);
-  float *fin = (float *)ws, *part = fin + 2 * C;
-  int rows_per_block;
-  dim3 grid = bn_grid(M, C, bn_reduce_cap(C), &rows_per_block);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x, M, C, ps_dy,
-                     ps_x, rows_per_block, scale, shift, mean, relu, part);
-  SN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(sn_div_up(C, 32)), dim3(kBnFinThreads), 0, s, (const float *)part, (int)grid.x, C,
-                     invstd, fin, dgamma, dbeta);
-  SN_CHECK_LAUNCH();
-  if (dx) {
-    grid = bn_grid(M, C, 8192, &rows_per_block);
-    hipLaunchKernelGGL(bn_bwd_dx_kernel, grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x,
-                       (const half_t *)accumulate, (half_t *)dx, M, C, ps_dy, ps_x, ps_acc, ps_dx, rows_per_block, scale, shift,
-                       mean, invstd, (const float *)fin + C, (const float *)fin, relu);
-    SN_CHECK_LAUNCH();
-  }
-  return SN_OK;
-}
-
-// sn_bn_backward with the reduction already done elsewhere (sn_conv_dgrad_bn: partials (nblk, 2, C) = sum g, sum g*(x-mean)
-// per row tile of the data-gradient convolution): finalize + dx only.
-SN_EXPORT int sn_bn_backward_blocks(const float *partials, int nblk, const void *dy, const void *x, const void *accumulate, void *dx,
-                                    int M, int C, int ps_dy, int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift,
-                                    const float *mean, const float *invstd, int relu, void *ws, float *dgamma, float *dbeta,
-                                    sn_stream_t stream) {
-  SN_REQUIRE(partials && nblk > 0 && dy && x && scale && shift && mean && invstd && ws && bn_shape_ok(C) && M > 0,
-             "sn_bn_backward_blocks: bad arguments (C=%d)", C);
-  hipStream_t s = sn_stream(stream);
-  float *fin = (float *)ws;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(sn_div_up(C, 32)), dim3(kBnFinThreads), 0, s, partials, nblk, C, invstd, fin, dgamma,
+// the tail of the two backward entry points: partials -> dgamma / dbeta and the dx coefficients (fin = the first 2C floats of ws), dx
+static int bn_bwd_finish(const float *part, int nblk, const void *dy, const void *x, const void *accumulate, void *dx, int M, int C,
+                         int ps_dy, int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean,
+                         const float *invstd, int relu, float *fin, float *dgamma, float *dbeta, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(sn_div_up(C, 32)), dim3(kBnFinThreads), 0, s, part, nblk, C, invstd, fin, dgamma,
                      dbeta);
   SN_CHECK_LAUNCH();
   if (dx) {
@@ -545,6 +504,37 @@ SN_EXPORT int sn_bn_backward_blocks(const float *partials, int nblk, const void 
     SN_CHECK_LAUNCH();
   }
   return SN_OK;
+}
+
+// Backward of y = relu?(BN_train(x)).  dgamma/dbeta (fp32, length C) are ACCUMULATED into (+=, the optimizer's
+// gradient arena is zeroed once per step); ws = sn_bn_workspace_bytes(M, C).  Three launches, no atomics, no memset:
+// partial reduce -> finalize -> dx.
+SN_EXPORT int sn_bn_backward(const void *dy, const void *x, const void *accumulate, void *dx, int M, int C, int ps_dy,
+                             int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift, const float *mean,
+                             const float *invstd, int relu, void *ws, float *dgamma, float *dbeta, sn_stream_t stream) {
+  SN_REQUIRE(dy && x && scale && shift && mean && invstd && ws && bn_shape_ok(C) && M > 0,
+             "sn_bn_backward: bad arguments (C=%d)", C);
+  hipStream_t s = sn_stream(stream);
+  float *fin = (float *)ws, *part = fin + 2 * C;
+  int rows_per_block;
+  const dim3 grid = bn_grid(M, C, bn_reduce_cap(C), &rows_per_block);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(kBnThreads), 0, s, (const half_t *)dy, (const half_t *)x, M, C, ps_dy,
+                     ps_x, rows_per_block, scale, shift, mean, relu, part);
+  SN_CHECK_LAUNCH();
+  return bn_bwd_finish(part, (int)grid.x, dy, x, accumulate, dx, M, C, ps_dy, ps_x, ps_acc, ps_dx, scale, shift, mean, invstd, relu, fin,
+                       dgamma, dbeta, s);
+}
+
+// sn_bn_backward with the reduction already done elsewhere (sn_conv_dgrad_bn: partials (nblk, 2, C) = sum g, sum g*(x-mean)
+// per row tile of the data-gradient convolution): finalize + dx only.
+SN_EXPORT int sn_bn_backward_blocks(const float *partials, int nblk, const void *dy, const void *x, const void *accumulate, void *dx,
+                                    int M, int C, int ps_dy, int ps_x, int ps_acc, int ps_dx, const float *scale, const float *shift,
+                                    const float *mean, const float *invstd, int relu, void *ws, float *dgamma, float *dbeta,
+                                    sn_stream_t stream) {
+  SN_REQUIRE(partials && nblk > 0 && dy && x && scale && shift && mean && invstd && ws && bn_shape_ok(C) && M > 0,
+             "sn_bn_backward_blocks: bad arguments (C=%d)", C);
+  return bn_bwd_finish(partials, nblk, dy, x, accumulate, dx, M, C, ps_dy, ps_x, ps_acc, ps_dx, scale, shift, mean, invstd, relu,
+                       (float *)ws, dgamma, dbeta, sn_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1100,7 +1090,7 @@ __global__ __launch_bounds__(256) void copy2d_kernel(const TI *__restrict__ in, 
 
 // the same copy, eight elements per thread (16-byte accesses of the fp16 side, 2 x 16 of an fp32 side): rows and pitches that
 // are multiples of 8 elements on 16-byte aligned pointers -- Concat slices (63 MB per step), the step's input copies (80 MB).
-// cpr8 = cols / 8; row index by multiplication (fd = conv_fastdiv_make(cpr8))
+// cpr8 = cols / 8; row index by multiplication (fd = sn_div_make(cpr8))
 template <typename T>
 __device__ __forceinline__ void load8(const T *p, float v[8]);
 template <>
@@ -1130,12 +1120,12 @@ __device__ __forceinline__ void store8<float>(float *p, const float v[8]) {
 }
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void copy2d_vec8_kernel(const TI *__restrict__ in, TO *__restrict__ out, long total8, int cpr8,
-                                                          int in_ld, int out_ld, unsigned fd_mul, unsigned fd_sh) {
+                                                          int in_ld, int out_ld, const SnDiv fd) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (long)gridDim.x * blockDim.x) {
     long r;
     int c;
     if (in_ld == cpr8 * 8 && out_ld == in_ld) { r = 0; c = 0; }      // contiguous on both sides: a flat copy
-    else if (i < (1l << 31)) { r = (long)(((unsigned long long)__umulhi((unsigned)i, fd_mul) + (unsigned)i) >> fd_sh); c = (int)(i - r * cpr8); }
+    else if (i < (1l << 31)) { r = (long)sn_div((unsigned)i, fd); c = (int)(i - r * cpr8); }
     else { r = i / cpr8; c = (int)(i - r * cpr8); }
     const size_t si = (in_ld == cpr8 * 8 && out_ld == in_ld) ? (size_t)i * 8 : (size_t)r * in_ld + (size_t)c * 8;
     const size_t di = (in_ld == cpr8 * 8 && out_ld == in_ld) ? (size_t)i * 8 : (size_t)r * out_ld + (size_t)c * 8;
@@ -1144,45 +1134,31 @@ __global__ __launch_bounds__(256) void copy2d_vec8_kernel(const TI *__restrict__
     store8<TO>(out + di, v);
   }
 }
-static void fastdiv_make_u32(unsigned d, unsigned &mul, unsigned &sh) {
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  mul = (unsigned)((((unsigned long long)1 << 32) * (((unsigned long long)1 << s) - d)) / d + 1);
-  sh = s;
+
+// one copy of a (TI, TO) pair: the 16-byte form when every row starts 16-byte aligned, else element by element
+template <typename TI, typename TO>
+static void copy2d_launch(const void *in, void *out, long rows, int cols, int in_ld, int out_ld, hipStream_t s) {
+  if (cols % 8 == 0 && (in_ld % 8 == 0 || rows == 1) && (out_ld % 8 == 0 || rows == 1) && ((uintptr_t)in % 16) == 0 &&
+      ((uintptr_t)out % 16) == 0) {
+    const int cpr8 = cols / 8;
+    const long total8 = rows * cpr8;
+    if (rows == 1) in_ld = out_ld = cols;
+    hipLaunchKernelGGL((copy2d_vec8_kernel<TI, TO>), dim3(ew_blocks(total8)), dim3(256), 0, s, (const TI *)in, (TO *)out, total8, cpr8,
+                       in_ld, out_ld, sn_div_make((unsigned)cpr8));
+  } else {
+    hipLaunchKernelGGL((copy2d_kernel<TI, TO>), dim3(ew_blocks(rows * cols)), dim3(256), 0, s, (const TI *)in, (TO *)out, rows, cols,
+                       in_ld, out_ld);
+  }
 }
 
 SN_EXPORT int sn_copy2d(const void *in, void *out, long rows, int cols, int in_ld, int out_ld, int in_dtype, int out_dtype,
                         sn_stream_t stream) {
   SN_REQUIRE(in && out && rows > 0 && cols > 0, "sn_copy2d: bad arguments");
   hipStream_t s = sn_stream(stream);
-  if (cols % 8 == 0 && (in_ld % 8 == 0 || rows == 1) && (out_ld % 8 == 0 || rows == 1) && ((uintptr_t)in % 16) == 0 &&
-      ((uintptr_t)out % 16) == 0) {
-    const int cpr8 = cols / 8;
-    const long total8 = rows * cpr8;
-    if (rows == 1) in_ld = out_ld = cols;
-    unsigned mul, sh;
-    fastdiv_make_u32((unsigned)cpr8, mul, sh);
-    const dim3 g(ew_blocks(total8));
-    if (in_dtype == 0 && out_dtype == 0)
-      hipLaunchKernelGGL((copy2d_vec8_kernel<half_t, half_t>), g, dim3(256), 0, s, (const half_t *)in, (half_t *)out, total8, cpr8, in_ld, out_ld, mul, sh);
-    else if (in_dtype == 0 && out_dtype == 1)
-      hipLaunchKernelGGL((copy2d_vec8_kernel<half_t, float>), g, dim3(256), 0, s, (const half_t *)in, (float *)out, total8, cpr8, in_ld, out_ld, mul, sh);
-    else if (in_dtype == 1 && out_dtype == 0)
-      hipLaunchKernelGGL((copy2d_vec8_kernel<float, half_t>), g, dim3(256), 0, s, (const float *)in, (half_t *)out, total8, cpr8, in_ld, out_ld, mul, sh);
-    else
-      hipLaunchKernelGGL((copy2d_vec8_kernel<float, float>), g, dim3(256), 0, s, (const float *)in, (float *)out, total8, cpr8, in_ld, out_ld, mul, sh);
-    SN_CHECK_LAUNCH();
-    return SN_OK;
-  }
-  const dim3 grid(ew_blocks(rows * cols));
-  if (in_dtype == 0 && out_dtype == 0)
-    hipLaunchKernelGGL((copy2d_kernel<half_t, half_t>), grid, dim3(256), 0, s, (const half_t *)in, (half_t *)out, rows, cols, in_ld, out_ld);
-  else if (in_dtype == 0 && out_dtype == 1)
-    hipLaunchKernelGGL((copy2d_kernel<half_t, float>), grid, dim3(256), 0, s, (const half_t *)in, (float *)out, rows, cols, in_ld, out_ld);
-  else if (in_dtype == 1 && out_dtype == 0)
-    hipLaunchKernelGGL((copy2d_kernel<float, half_t>), grid, dim3(256), 0, s, (const float *)in, (half_t *)out, rows, cols, in_ld, out_ld);
-  else
-    hipLaunchKernelGGL((copy2d_kernel<float, float>), grid, dim3(256), 0, s, (const float *)in, (float *)out, rows, cols, in_ld, out_ld);
+  if (in_dtype == 0 && out_dtype == 0) copy2d_launch<half_t, half_t>(in, out, rows, cols, in_ld, out_ld, s);
+  else if (in_dtype == 0 && out_dtype == 1) copy2d_launch<half_t, float>(in, out, rows, cols, in_ld, out_ld, s);
+  else if (in_dtype == 1 && out_dtype == 0) copy2d_launch<float, half_t>(in, out, rows, cols, in_ld, out_ld, s);
+  else copy2d_launch<float, float>(in, out, rows, cols, in_ld, out_ld, s);
   SN_CHECK_LAUNCH();
   return SN_OK;
 }
@@ -1346,7 +1322,6 @@ __global__ __launch_bounds__(256) void sgd_dev_vec4_kernel(float4 *__restrict__ 
                                                            float4 *__restrict__ mom, half_t *__restrict__ w16, long n4,
                                                            const float *__restrict__ hyper, float lr_mult, float wd_mult) {
   const float lr = hyper[0] * lr_mult, wd = hyper[1] * wd_mult, momentum = hyper[2], rescale = hyper[3];
-  typedef half_t half4 __attribute__((ext_vector_type(4)));
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const float4 w = w32[i], g4 = grad[i], m4 = mom[i];
     float4 nm, nw;
@@ -1492,7 +1467,7 @@ SN_EXPORT int sn_ew_f32(const float *a, const float *b, float *out, long n, int 
 }
 
 // bias gradient: db[c] += sum over rows of dy[r][c]   (dy fp16 or fp32, row stride ld)
-// Row blocks write partial sums [row block][C]; bias_grad_finish_kernel adds them to db in block order: no atomics, the
+// Row blocks write partial sums [row block][C]; sn_partial_sum adds them to db in block order: no atomics, the
 // same bits every run.  Without scratch one block per 64 channels walks all rows and adds its sum to db itself.
 template <typename T>
 __global__ __launch_bounds__(256) void bias_grad_kernel(const T *__restrict__ dy, float *__restrict__ db, float *__restrict__ part,
@@ -1555,27 +1530,9 @@ __global__ __launch_bounds__(256) void bias_grad_vec8_kernel(const half_t *__res
   }
 }
 
-__global__ __launch_bounds__(256) void bias_grad_finish_kernel(const float *__restrict__ part, int nblk, int C, float *__restrict__ db) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  // the row blocks are added in block order (fixed bits), but their loads are independent: eight in flight instead of a chain
-  // of nblk dependent L2 round trips (13.5 us for 96 blocks)
-  float s = 0.f;
-  int k = 0;
-  for (; k + 8 <= nblk; k += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(k + u) * C + c];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < nblk; ++k) s += part[(size_t)k * C + c];
-  db[c] += s;
-}
-
 static int bias_grad_blocks(long rows, long *rows_per_block) {
   int by = (int)((rows + 255) / 256);
-  if (by > 96) by = 96;      // the finish kernel walks the row blocks serially per channel
+  if (by > 96) by = 96;      // sn_partial_sum walks the row blocks serially per channel
   if (by < 1) by = 1;
   *rows_per_block = (rows + by - 1) / by;
   return (int)((rows + *rows_per_block - 1) / *rows_per_block);
@@ -1614,9 +1571,5 @@ SN_EXPORT int sn_bias_grad(const void *dy, float *db, long rows, int C, int ld, 
   else
     hipLaunchKernelGGL((bias_grad_kernel<float>), grid, dim3(256), 0, s, (const float *)dy, db, part, rows, C, ld, rpb);
   SN_CHECK_LAUNCH();
-  if (part) {
-    hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(sn_div_up(C, 256)), dim3(256), 0, s, (const float *)part, by, C, db);
-    SN_CHECK_LAUNCH();
-  }
-  return SN_OK;
+  return part ? sn_partial_sum(part, by, C, db, s) : SN_OK;
 }

@@ -41,11 +41,6 @@ SN_EXPORT size_t sn_proposal_workspace_bytes(int B, int A, int Fh, int Fw, int p
   return prop_layout(B, A, Fh, Fw, pre_nms_top_n, post_nms_top_n).bytes;
 }
 
-__device__ __forceinline__ unsigned orderable(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending-order preserving
-}
-
 // K1: decode + sort keys.  cls_prob (B,2,A*Fh,Fw), bbox_pred (B,4A,Fh,Fw), both fp32 reference layout.
 __global__ __launch_bounds__(256) void proposal_decode_kernel(const float *__restrict__ cls_prob, const float *__restrict__ bbox_pred,
                                                               const float *__restrict__ im_info, const float *__restrict__ base,
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void proposal_decode_kernel(const float *__res
   float *o = boxes_all + ((size_t)b * total + i) * 4;
   o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
   // descending score, ascending index on ties
-  kb[i] = ((unsigned long long)(~orderable(score)) << 32) | (unsigned)i;
+  kb[i] = ((unsigned long long)(~sn_float_key(score)) << 32) | (unsigned)i;
 }
 
 // K2: in-place ascending bitonic sort of sort_n (power of two) 64-bit keys, one workgroup per image.
@@ -240,7 +235,7 @@ __global__ __launch_bounds__(256) void proposal_gather_kernel(const float *__res
   const unsigned long long key = keys[(size_t)b * sort_n + r];
   const unsigned idx = (unsigned)(key & 0xffffffffu);
   const unsigned ob = ~(unsigned)(key >> 32);
-  const unsigned u = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;  // inverse of orderable()
+  const unsigned u = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;  // inverse of sn_float_key()
   const float *s = boxes_all + ((size_t)b * total + idx) * 4;
   float *o = sorted + ((size_t)b * pre + r) * 5;
   o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3]; o[4] = __uint_as_float(u);

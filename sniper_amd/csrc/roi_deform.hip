@@ -12,8 +12,6 @@
 
 #include <stdlib.h>
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------
 // DeformablePSROIPooling, group_size == 1 (the only setting the reference's symbols use).
@@ -115,10 +113,6 @@ __device__ __forceinline__ float tent_dsum(const AxisSamplesT<SM> &a, int x) {
   return s;
 }
 
-// sum[q] += w * (float)v[q], q = 0..7, as eight v_fma_mix_f32: the fp16 operand is converted inside the FMA (hipcc emits
-// 8 v_cvt_f32_f16 + 4 v_pk_fma_f32 for the plain expression: 12 instructions per window cell against 8; same bits, subnormals
-// included -- tools/probes/fma_mix_probe.hip)
-typedef float roi_floatx4 __attribute__((ext_vector_type(4)));
 // sum_q u[q] * g[q] over a lane's eight channels as four v_dot2_f32_f16 (fp16 pairs, fp32 accumulate; products exact) instead of
 // 8 conversions + 8 FMAs
 typedef _Float16 roi_half2 __attribute__((ext_vector_type(2)));
@@ -129,8 +123,11 @@ __device__ __forceinline__ float dot8(half8 u, half8 g) {
     d = __builtin_amdgcn_fdot2(roi_half2{u[2 * k], u[2 * k + 1]}, roi_half2{g[2 * k], g[2 * k + 1]}, d, false);
   return d;
 }
+// sum[q] += w * (float)v[q], q = 0..7, as eight v_fma_mix_f32: the fp16 operand is converted inside the FMA (hipcc emits
+// 8 v_cvt_f32_f16 + 4 v_pk_fma_f32 for the plain expression: 12 instructions per window cell against 8; same bits, subnormals
+// included -- tools/probes/fma_mix_probe.hip)
 __device__ __forceinline__ void fma_mix8(float (&sum)[8], float w, half8 v) {
-  const roi_floatx4 p = __builtin_bit_cast(roi_floatx4, v);
+  const floatx4 p = __builtin_bit_cast(floatx4, v);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[0,1,0]" : "+v"(sum[2 * k]) : "v"(w), "v"(p[k]));
@@ -552,7 +549,6 @@ __global__ __launch_bounds__(256) void dpsroi_bwd_data_kernel(const half_t *__re
 // (w = hi + lo to 2^-22: the fp32 output keeps its 1e-3 contract) and one K-step is 8 v_mfma_f32_16x16x32_f16 per wave
 // on gathered dout values (B operand: lane (channel n, k-group) holds its channel's value of 8 consecutive entries).
 // Same windows, same entry order, fixed accumulation order: deterministic.
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int kMfmaK = 64;     // bins of one RoI (pooled * pooled) this kernel handles
 constexpr int kListCap = 384;  // entries collected before they are multiplied: >= 4 RoIs x 49 bins beyond the flush threshold
 constexpr int kListPitch = kListCap + 8;   // halves per cell row: 16-byte reads of the 16 rows fall on 16 different bank quads
@@ -828,10 +824,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // workgroup size of the per-RoI kernels (threads; a multiple of 64, >= the bin count; 64, 128 and 512 were slower,
 // profiles/r06_kab_dpsroi_block.txt)
 constexpr int kRoiBlock = 256;
-static long blocks_for(long total) {
-  long b = (total + 255) / 256;
-  return b < 1 ? 1 : (b > 16384 ? 16384 : b);
-}
+static int blocks_for(long total) { return sn_blocks(total, 16384); }
 
 SN_EXPORT int sn_dpsroi_pool_fwd(const void *data, const float *rois, const float *trans, void *out, int R, int H, int W, int C,
                                  int pooled, int sample_per_part, float spatial_scale, float trans_std, sn_stream_t stream) {
@@ -844,7 +837,7 @@ SN_EXPORT int sn_dpsroi_pool_fwd(const void *data, const float *rois, const floa
     hipLaunchKernelGGL(dpsroi_fwd_roi_kernel<kMaxS>, dim3((unsigned)R), dim3(256), 0, sn_stream(stream), (const half_t *)data, rois, trans,
                        (half_t *)out, R, H, W, C, pooled, sample_per_part, spatial_scale, trans_std);
   else
-    hipLaunchKernelGGL(dpsroi_fwd_kernel, dim3((unsigned)blocks_for((long)R * pooled * pooled * (C / 8))), dim3(256), 0,
+    hipLaunchKernelGGL(dpsroi_fwd_kernel, dim3(blocks_for((long)R * pooled * pooled * (C / 8))), dim3(256), 0,
                        sn_stream(stream), (const half_t *)data, rois, trans, (half_t *)out, R, H, W, C, pooled, sample_per_part,
                        spatial_scale, trans_std);
   SN_CHECK_LAUNCH();
@@ -1188,7 +1181,7 @@ SN_EXPORT int sn_psroi_pool_fwd(const void *data, const float *rois, const float
                        (const half_t *)data, rois, trans, (half_t *)out, R, H, W, C, pooled, sample_per_part, group_size, output_dim,
                        spatial_scale, trans_std, group_major ? 1 : 0);
   } else {
-    hipLaunchKernelGGL(psroi_ps_fwd_kernel<false>, dim3((unsigned)blocks_for((long)R * pooled * pooled * output_dim)), dim3(256), 0,
+    hipLaunchKernelGGL(psroi_ps_fwd_kernel<false>, dim3(blocks_for((long)R * pooled * pooled * output_dim)), dim3(256), 0,
                        sn_stream(stream), (const half_t *)data, rois, trans, (half_t *)out, R, H, W, C, pooled, sample_per_part,
                        group_size, output_dim, spatial_scale, trans_std, group_major ? 1 : 0);
   }
@@ -1496,17 +1489,17 @@ SN_EXPORT int sn_deform_im2col(const void *data, const void *offset, void *col, 
                                sn_stream_t stream) {
   SN_REQUIRE(data && offset && col && C % 8 == 0 && deformable_groups > 0 && (C / deformable_groups) % 8 == 0,
              "sn_deform_im2col: bad arguments");
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Ho = sn_conv_out(H, KH, stride, pad, dil), Wo = sn_conv_out(W, KW, stride, pad, dil);
   const long total = (long)N * Ho * Wo * KH * KW * (C / 8);
   SN_REQUIRE(total < 2147483647L, "sn_deform_im2col: too many column elements for 32-bit indexing");
   const SnDiv d_cpr = sn_div_make(C / 8), d_T = sn_div_make(KH * KW), d_Wo = sn_div_make(Wo), d_Ho = sn_div_make(Ho),
               d_KW = sn_div_make(KW), d_cg = sn_div_make(C / deformable_groups);
   if (offset_dtype == 0)
-    hipLaunchKernelGGL((deform_im2col_kernel<half_t>), dim3((unsigned)blocks_for(total)), dim3(256), 0, sn_stream(stream),
+    hipLaunchKernelGGL((deform_im2col_kernel<half_t>), dim3(blocks_for(total)), dim3(256), 0, sn_stream(stream),
                        (const half_t *)data, (const half_t *)offset, (half_t *)col, N, H, W, C, Ho, Wo, KH, KW, stride, pad, dil,
                        deformable_groups, offset_pix_stride, d_cpr, d_T, d_Wo, d_Ho, d_KW, d_cg);
   else
-    hipLaunchKernelGGL((deform_im2col_kernel<float>), dim3((unsigned)blocks_for(total)), dim3(256), 0, sn_stream(stream),
+    hipLaunchKernelGGL((deform_im2col_kernel<float>), dim3(blocks_for(total)), dim3(256), 0, sn_stream(stream),
                        (const half_t *)data, (const float *)offset, (half_t *)col, N, H, W, C, Ho, Wo, KH, KW, stride, pad, dil,
                        deformable_groups, offset_pix_stride, d_cpr, d_T, d_Wo, d_Ho, d_KW, d_cg);
   SN_CHECK_LAUNCH();
@@ -1543,7 +1536,7 @@ SN_EXPORT int sn_deform_col2im(const void *dcol, const void *data, const void *o
   SN_REQUIRE(dcol && data && offset && C % 8 == 0 && deformable_groups > 0 && N > 0, "sn_deform_col2im: bad arguments");
   SN_REQUIRE(C % deformable_groups == 0, "sn_deform_col2im: C must be a multiple of the deformable groups");
   const int cg = C / deformable_groups, lpg = cg / 8;
-  const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int Ho = sn_conv_out(H, KH, stride, pad, dil), Wo = sn_conv_out(W, KW, stride, pad, dil);
   SN_REQUIRE((long)N * Ho * Wo * KH * KW < 2147483647L, "sn_deform_col2im: too many sampling points");
   hipStream_t s = sn_stream(stream);
   if (d_offset) {

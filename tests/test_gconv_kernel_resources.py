@@ -1,12 +1,14 @@
-"""CPU: register budgets of the grouped-convolution kernels (csrc/gconv.hip), from the compiler's resource remarks."""
+"""CPU: register budgets of the grouped-convolution kernels (csrc/gconv.hip and the ordered partial sum its weight gradient
+finishes with, csrc/common.hip), from the compiler's resource remarks."""
 from test_kernel_resources import _resources
 
 
 def test_gconv_kernels_keep_everything_in_registers():
     res = _resources('gconv')
+    res.update({k: v for k, v in _resources('common').items() if 'partial_sum_kernel' in k})
     mfma = {k: v for k, v in res.items() if 'gconv_mfma_kernel' in k}
     wgrad = {k: v for k, v in res.items() if 'gconv_wgrad_mfma_kernel' in k}
-    plain = {k: v for k, v in res.items() if 'gconv_plain_' in k or 'gconv_wgrad_finish' in k}
+    plain = {k: v for k, v in res.items() if 'gconv_plain_' in k or 'partial_sum_kernel' in k}
     assert len(mfma) == 4 and len(wgrad) == 4 and len(plain) == 4, sorted(res)       # {1x1, 3x3} x {fwd, dgrad}; {1x1, 3x3} x {Cg<=16, 32}
     assert len(res) == 12, sorted(res)
     for name, r in res.items():

@@ -1,7 +1,7 @@
 """-m gpu: the hot kernels at the LAUNCH SHAPES of BASELINE configs[1] (ResNet-101, 20 chips of 512 x 512 per GPU) against
 the fp32 CPU oracle, element by element -- not properties (tests/test_gpu_fullsize_properties.py), not small tiles
 (tests/test_gpu_nn_ops.py).  These are the shapes whose kernel selection differs from the small cases: the measured
-per-layer LDS-DMA tile configurations (conv_dma_choice), the weight gradient's K-splits over 20 480 / 81 920 pixels with
+per-layer LDS-DMA tile configurations (conv_dma_choice_balanced), the weight gradient's K-splits over 20 480 / 81 920 pixels with
 slab reduction, the all-taps 3x3 weight gradient of the RPN, 6000-RoI deformable PS-RoI pooling.
 Tolerance everywhere: 1e-2 relative to the tensor's scale (north_star: conv / loss tensors within 1e-2 rel, fp16 storage)."""
 import numpy as np

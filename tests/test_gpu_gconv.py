@@ -91,6 +91,46 @@ def test_grouped_conv_vs_torch(N, C, O, g, H, W, K, s, p, d, extra):
     assert_close(dw.cpu().numpy(), 2 * want_dw, 1e-2, 1e-2 * np.abs(2 * want_dw).max(), 'gconv wgrad accumulates')
 
 
+# (C, O, groups) and the (N, H, W) of 3x3 / stride 1 / pad 1 problems whose pixel-block counts are 4, 8 and 11
+_FINISH = [
+    ('mfma', 64, 64, 2, [(1, 10, 10), (1, 15, 15), (2, 13, 13)]),        # Cg = 32: one block per 32-pixel chunk
+    ('plain', 24, 48, 4, [(1, 15, 15), (2, 15, 16), (2, 18, 19)]),       # Cg = 6, Og = 12: blocks of about 64 pixels
+]
+
+
+def test_grouped_wgrad_partial_sum_block_counts():
+    """The ordered finish of sn_gconv_wgrad (sn_partial_sum, shared with the depthwise weight gradient and the bias gradient) over
+    every loop shape of its block walk, behind the MFMA and the plain kernel: pixel-block counts (the workspace query over 4 bytes
+    x the weight count) below 8, a multiple of 8 and above 8 but no multiple; `dw +=` on a non-zero dw against the float64
+    gradient, the same bits on a second call."""
+    hip = _hip()
+    for path, C, O, g, shapes in _FINISH:
+        Cg, nw = C // g, O * 9 * (C // g)
+        rs = np.random.RandomState(C + g)
+        w = torch.zeros((O, Cg, 3, 3), dtype=torch.float64, requires_grad=True)
+        dw0 = torch.from_numpy(rs.standard_normal((O, 9, Cg)).astype(np.float32)).to(dev())
+        counts = []
+        for (N, H, W) in shapes:
+            x = rs.standard_normal((N, C, H, W)).astype(np.float32)
+            dy = rs.standard_normal((N, O, H, W)).astype(np.float32)
+            w.grad = None
+            Fnn.conv2d(torch.from_numpy(f16r(x)).double(), w, None, 1, 1, 1, groups=g).backward(torch.from_numpy(f16r(dy)).double())
+            want = dw0.double().cpu().numpy() + w.grad.numpy().transpose(0, 2, 3, 1).reshape(O, 9, Cg)
+            xd, dyd = to_nhwc_f16(x), to_nhwc_f16(dy)
+            need = hip.query('sn_gconv_wgrad_workspace_bytes', N, H, W, C, O, g, 3, 3, 1, 1, 1)
+            counts.append(need // (4 * nw))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev())
+            runs = []
+            for rep in range(2):
+                dw = dw0.clone()
+                hip.call('sn_gconv_wgrad', dyd, xd, dw, N, H, W, C, O, O, C, g, 3, 3, 1, 1, 1, ws, need, hip.stream())
+                runs.append(dw)
+            assert torch.equal(runs[0], runs[1]), (path, N, H, W)
+            assert_close(runs[0].cpu().numpy(), want, 1e-2, 1e-2 * np.abs(want).max(), 'gconv wgrad finish %s %dx%dx%d' % (path, N, H, W))
+        assert counts == [4, 8, 11], (path, counts)
+        assert any(b < 8 for b in counts) and any(b % 8 == 0 for b in counts) and any(b > 8 and b % 8 for b in counts), (path, counts)
+
+
 def test_grouped_conv_fp32_output():
     """a head-style grouped layer whose consumer wants fp32: the plain kernel writes it"""
     hip = _hip()

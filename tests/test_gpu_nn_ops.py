@@ -303,6 +303,52 @@ def test_bias_grad_fp16_paths(rows, C, ld):
     assert_close(db1.cpu().numpy(), want, 1e-4, 1e-3 * max(1.0, np.sqrt(rows) / 10), 'bias grad fp16 without scratch')
 
 
+def _covers_partial_sum_loops(block_counts):
+    """sn_partial_sum adds the blocks eight at a time and the rest one by one: a count below 8 (the tail alone), a multiple of 8
+    (the unrolled loop alone) and a count above 8 that is not a multiple (both)"""
+    return (any(b < 8 for b in block_counts) and any(b % 8 == 0 for b in block_counts) and
+            any(b > 8 and b % 8 for b in block_counts))
+
+
+@pytest.fixture(scope='module')
+def bias_grad_case():
+    """one fp16 gradient of 2400 rows x 64 channels at a pitch of 64 (16-byte form) and of 68 (element form), shared and unchanged"""
+    rs = np.random.RandomState(64)
+    dy = torch.from_numpy(rs.standard_normal((2400, 68)).astype(np.float32)).to(dev()).half()
+    return {64: dy[:, :64].contiguous(), 68: dy}, torch.from_numpy(rs.standard_normal(64).astype(np.float32)).to(dev())
+
+
+def test_bias_grad_partial_sum_block_counts(bias_grad_case):
+    """The ordered finish of sn_bias_grad (sn_partial_sum, shared with the depthwise and grouped weight gradients) over every loop
+    shape of its block walk, on the 16-byte and the element form: `db +=` on a non-zero db against the float64 column sum, the
+    same bits on a second call.  The 16-byte form uses as many row blocks as the workspace query sizes for; the element form keeps
+    the 256-row blocks of bias_grad_blocks (at most 96), so its count is stated by that rule."""
+    hip = _hip()
+    dys, db0 = bias_grad_case
+    C = 64
+    counts = {64: [], 68: []}
+    for rows in (300, 600, 1000, 2000, 2400):
+        need = hip.query('sn_bias_grad_workspace_bytes', rows, C)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev())
+        for ld in (64, 68):
+            if ld == 64:
+                counts[ld].append(need // (4 * C))
+            else:
+                rpb = -(-rows // min(96, -(-rows // 256)))
+                counts[ld].append(-(-rows // rpb))
+            dyd = dys[ld][:rows]
+            want = db0.double().cpu().numpy() + dyd[:, :C].double().sum(0).cpu().numpy()
+            runs = []
+            for rep in range(2):
+                db = db0.clone()
+                hip.call('sn_bias_grad', dyd, db, rows, C, ld, 0, ws, need, hip.stream())
+                runs.append(db)
+            assert torch.equal(runs[0], runs[1]), (rows, ld)
+            assert_close(runs[0].cpu().numpy(), want, 1e-4, 1e-3 * max(1.0, np.sqrt(rows) / 10), 'bias grad finish rows=%d ld=%d' % (rows, ld))
+    assert counts[64] == [5, 10, 16, 32, 38] and counts[68] == [2, 3, 4, 8, 10], counts
+    assert _covers_partial_sum_loops(counts[64]) and _covers_partial_sum_loops(counts[68]), counts
+
+
 def test_batchnorm_train_fwd_bwd():
     hip = _hip()
     rs = np.random.RandomState(3)
@@ -1174,6 +1220,36 @@ def test_depthwise_conv_vs_torch(N, C, H, W, s):
     assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
     want_dw = wt.grad.numpy().reshape(C, 9)
     assert_close(dw.cpu().numpy(), want_dw, 1e-2, 1e-2 * np.abs(want_dw).max(), 'dw wgrad')
+
+
+def test_depthwise_wgrad_partial_sum_block_counts():
+    """The ordered finish of sn_dwconv_wgrad (sn_partial_sum) over every loop shape of its block walk: pixel-block counts (the
+    workspace query over 4 bytes x C x 9 weights) below 8, a multiple of 8 and above 8 but no multiple; `dw +=` on a non-zero dw
+    against the float64 gradient, the same bits on a second call."""
+    hip = _hip()
+    C = 32
+    rs = np.random.RandomState(C)
+    w = torch.zeros((C, 1, 3, 3), dtype=torch.float64, requires_grad=True)
+    dw0 = torch.from_numpy(rs.standard_normal((C, 9)).astype(np.float32)).to(dev())
+    counts = []
+    for (N, H, W) in ((1, 56, 56), (2, 59, 65), (3, 56, 56)):
+        x = rs.standard_normal((N, C, H, W)).astype(np.float32)
+        dy = rs.standard_normal((N, C, H, W)).astype(np.float32)
+        w.grad = None
+        Fnn.conv2d(torch.from_numpy(f16r(x)).double(), w, None, 1, 1, 1, groups=C).backward(torch.from_numpy(f16r(dy)).double())
+        want = dw0.double().cpu().numpy() + w.grad.numpy().reshape(C, 9)
+        xd, dyd = to_nhwc_f16(x), to_nhwc_f16(dy)
+        need = hip.query('sn_dwconv_wgrad_workspace_bytes', N, H, W, C, 3, 3, 1, 1, 1)
+        counts.append(need // (4 * C * 9))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev())
+        runs = []
+        for rep in range(2):
+            dw = dw0.clone()
+            hip.call('sn_dwconv_wgrad', dyd, xd, dw, N, H, W, C, C, C, 3, 3, 1, 1, 1, ws, need, hip.stream())
+            runs.append(dw)
+        assert torch.equal(runs[0], runs[1]), (N, H, W)
+        assert_close(runs[0].cpu().numpy(), want, 1e-2, 1e-2 * np.abs(want).max(), 'dw wgrad finish %dx%dx%d' % (N, H, W))
+    assert counts == [4, 8, 10] and _covers_partial_sum_loops(counts), counts
 
 
 def test_clip_and_bn_relu6():
