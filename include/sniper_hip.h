@@ -415,6 +415,26 @@ int sn_softmax_output_bwd(const float *p, const float *label, float *grad, long 
 int sn_smooth_l1_loss(const float *pred, const float *target, const float *weight, float *loss, float *dpred, long n, float sigma,
                       float grad_scale, sn_stream_t stream);
 
+/* BoxAnnotatorOHEM (lib/operator_py/box_annotator_ohem.py:27-78; TRAIN.ENABLE_OHEM): per image keep the roi_per_img RoIs of largest
+ * classification + box loss and ignore the rest.  cls_score (B,R,C), bbox_pred / bbox_targets / bbox_weights (B,R,box_dim),
+ * labels (B,R): fp32, dense, device.  Outputs labels_ohem (B,R), bbox_weights_ohem (B,R,box_dim) and fg_labels (B,R) or NULL are
+ * OVERWRITTEN (every element written exactly once: no fill before the call) and may not alias the inputs.  Per image:
+ *   valid = label >= 0
+ *   loss  = valid ? -log(softmax(score)[label] + 1e-14) + sum_j w_j * smooth_l1(pred_j - target_j, sigma = 1) : 0
+ *           (fp32, max-subtracted log-sum-exp; a label >= C reads class C-1, nothing is read out of bounds)
+ *   the roi_per_img RoIs of largest loss are kept: weights unchanged, label unchanged (a label < 0 is written as -1);
+ *   every other RoI gets label -1 and weights 0.  fg_labels = labels_ohem with 0 replaced by -1.
+ * Order, where numpy's argsort leaves it open: descending loss, equal losses by ascending RoI index; a NaN loss ranks above every
+ * number (np.argsort puts NaN last, the reference reverses the order).
+ * roi_per_img >= R keeps everything.  Refused before any launch: a NULL tensor other than fg_labels, B < 1, R < 1,
+ * R > SN_OHEM_MAX_ROIS (the keys of one image are ranked in the 64 KB of LDS a workgroup gets without an opt-in), C < 2,
+ * box_dim < 1, roi_per_img < 1.
+ * One launch (one workgroup per image), no workspace, no atomics, no host read-back, the same bits every run.  No gradient. */
+#define SN_OHEM_MAX_ROIS 16384
+int sn_box_annotator_ohem(const float *cls_score, const float *bbox_pred, const float *labels, const float *bbox_targets,
+                          const float *bbox_weights, float *labels_ohem, float *bbox_weights_ohem, float *fg_labels /* or NULL */,
+                          int B, int R, int C, int box_dim, int roi_per_img, sn_stream_t stream);
+
 /* MultiProposal (:347-355) / MultiProposalTarget (:283-284).  cls_prob (B,2,A*Fh,Fw), bbox_pred (B,4A,Fh,Fw),
  * im_info (B,3), gt_boxes (B,G,5), valid_ranges (B,2), base_anchors (A,4): all fp32 device. */
 size_t sn_proposal_workspace_bytes(int B, int A, int Fh, int Fw, int pre_nms_top_n, int post_nms_top_n);

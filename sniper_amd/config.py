@@ -63,6 +63,8 @@ def _base():
         'RPN_BATCH_SIZE': 256, 'RPN_FG_FRACTION': 0.5, 'RPN_POSITIVE_OVERLAP': 0.5, 'RPN_NEGATIVE_OVERLAP': 0.4,
         'RPN_NMS_THRESH': 0.7, 'RPN_PRE_NMS_TOP_N': 6000, 'RPN_POST_NMS_TOP_N': 300, 'RPN_MIN_SIZE': 0,
         'BBOX_MEANS': (0.0, 0.0, 0.0, 0.0), 'BBOX_STDS': (0.1, 0.1, 0.2, 0.2),
+        # online hard example mining (default_configs.py; every shipped yml sets BATCH_ROIS_OHEM: 256)
+        'ENABLE_OHEM': False, 'BATCH_ROIS_OHEM': 256,
     }
     c.TEST = {
         'SCALES': ((1400, 2000), (800, 1280), (480, 512)), 'VALID_RANGES': ((-1, 90), (32, 180), (75, -1)),

@@ -117,7 +117,7 @@ class Param(object):
 
 
 _F32_CONSUMERS = {'Reshape', 'SoftmaxOutput', 'SoftmaxActivation', 'smooth_l1', 'MakeLoss', 'MultiProposal',
-                  'MultiProposalTarget', 'BlockGrad', '_mul_scalar', '_plus_scalar', '_minus_scalar', 'Flatten', 'Custom'}
+                  'MultiProposalTarget', 'BlockGrad', '_mul_scalar', '_plus_scalar', '_minus_scalar', 'Flatten', 'Custom', 'BoxAnnotatorOHEM'}
 _PRODUCES_ACT = {'Convolution', 'FullyConnected', 'BatchNorm', 'Activation', 'Pooling', 'Concat', 'DeformableConvolution',
                  'DeformablePSROIPooling', 'clip', 'Deconvolution', 'pick'}
 

@@ -1270,6 +1270,34 @@ class MaskRcnnTargetStep(Step):
                  self.max_gts, self.max_len, self.ms, self.outs[0].t, self.outs[1].t, hip.stream())
 
 
+@register('BoxAnnotatorOHEM')
+class BoxAnnotatorOHEMStep(Step):
+    """Online hard example mining on the device (box_annotator_ohem.py:27-78; semantics and the tie / NaN order: DESIGN.md
+    section 15): one sn_box_annotator_ohem call.  No gradient reaches any input (:80-83 assigns zeros) and the outputs are labels
+    and weights (needs_grad stays False), so there is no backward."""
+
+    def setup(self):
+        names = ('cls_score', 'bbox_pred', 'labels', 'bbox_targets', 'bbox_weights')
+        self.args = [self.data_in(k) for k in names]
+        score, pred, lab = self.args[0].shape, self.args[1].shape, self.args[2].shape
+        if len(score) != 3 or len(pred) != 3 or tuple(score[:2]) != tuple(pred[:2]) or tuple(lab) != tuple(score[:2]):
+            raise ValueError('%s: cls_score (B,R,C), bbox_pred (B,R,box_dim) and labels (B,R) expected, got %s %s %s' % (
+                self.node.name, score, pred, lab))
+        for v in self.args[3:]:
+            if tuple(v.shape) != tuple(pred):
+                raise ValueError('%s: %s has shape %s, bbox_pred %s' % (self.node.name, v.name, v.shape, pred))
+        self.B, self.R, self.C = score
+        self.box_dim = pred[2]
+        self.k = int(self.a['roi_per_img'])
+        self.outs = [self.new_out('f32', i) for i in range(self.node.num_outputs)]
+
+    def forward(self):
+        ex = self.ex
+        fg = self.outs[2].t if len(self.outs) > 2 else None
+        hip.call('sn_box_annotator_ohem', *[ex.as_f32(v) for v in self.args], self.outs[0].t, self.outs[1].t, fg, self.B, self.R,
+                 self.C, self.box_dim, self.k, hip.stream())
+
+
 @register('Deconvolution')
 class DeconvolutionStep(Step):
     """2x2 / stride-2 up-sampling of the mask head (:247-248): every input pixel writes its own 2x2 output block, so the

@@ -159,6 +159,9 @@ def infer_node(node, ins, shapes_of_var):
         if 'index' in pos and ins[pos['index']] is None:
             par[pos['index']] = tuple(d for i, d in enumerate(x) if i != axis)
         return [out], par
+    if op == 'BoxAnnotatorOHEM':         # box_annotator_ohem.py:103-114: the shapes of `labels` / `bbox_weights`
+        lab, wgt = tuple(ins[pos['labels']]), tuple(ins[pos['bbox_weights']])
+        return [lab, wgt, lab][:node.num_outputs], par
     if op == 'Custom':
         from ..mx import operator as _operator
         prop = _operator.get_prop(a.get('op_type'), a)

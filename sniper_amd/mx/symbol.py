@@ -9,6 +9,7 @@ because the reference addresses parameters by those names (init_weight_rcnn, FIX
 checkpoint_callback).
 """
 import collections
+import sys
 import threading
 
 import numpy as np
@@ -91,12 +92,15 @@ _OPS = {
     'MultiProposalTargetMask': (['cls_prob', 'bbox_pred', 'im_info', 'gt_boxes', 'valid_ranges'], [], 6),
     'MaskRcnnTarget': (['rois', 'mask_polys', 'mask_ids'], [], 2),
     'pick': (['data', 'index'], [], 1),
+    # lib/operator_py/box_annotator_ohem.py:86-120 as a native operator (a third output with get_fg_labels: _num_outputs)
+    'BoxAnnotatorOHEM': (['cls_score', 'bbox_pred', 'labels', 'bbox_targets', 'bbox_weights'], [], 2),
 }
 _OUT_NAMES = {
     'MultiProposal': ['output', 'score'],
     'MultiProposalTarget': ['output', 'label', 'bbox_target', 'bbox_weight'],
     'MultiProposalTargetMask': ['output', 'label', 'bbox_target', 'bbox_weight', 'mask_rois', 'mask_ids'],
     'MaskRcnnTarget': ['mask_targets', 'mask_cls'],
+    'BoxAnnotatorOHEM': ['labels_ohem', 'bbox_weights_ohem', 'fg_labels_ohem'],
 }
 _PARAM_INPUTS = {'weight', 'bias', 'gamma', 'beta'}
 _HINTS = {'_plus': '_plus', '_minus': '_minus', '_mul': '_mul', 'elemwise_add': 'elemwise_add'}
@@ -287,6 +291,8 @@ def _create(op, pos_inputs, kwargs):
         node = Node(op, name, kwargs, [_single(s, op) for s in ins], nout)
         return Symbol([(node, 0)]) if nout == 1 else Symbol([(node, i) for i in range(nout)])
     in_names, aux_names, nout = _OPS[op]
+    if op == 'BoxAnnotatorOHEM' and _bool(kwargs.get('get_fg_labels', False)):
+        nout = 3
     name = name or _auto_name(_HINTS.get(op, op.lower()))
     given = {}
     for k, s in zip(in_names, pos_inputs):
@@ -374,3 +380,4 @@ def __getattr__(name):  # module-level: mx.sym.<AnyOp>
 
 
 concat = Concat
+contrib = sys.modules[__name__]      # mx.sym.contrib.<Op> is mx.contrib.sym.<Op>: one operator table

@@ -120,14 +120,20 @@ class mobilenetv2_e2e(Symbol):
                 cls_prob=rpn_cls_prob, bbox_pred=rpn_bbox_pred, im_info=im_info, gt_boxes=gt_boxes, valid_ranges=valid_ranges,
                 crowd_boxes=crowd_boxes, batch_size=B, feature_stride=cfg.network.RPN_FEAT_STRIDE,
                 scales=cfg.network.ANCHOR_SCALES, name='multi_proposal_target')
-            label = mx.symbol.Reshape(data=label, shape=(-1,), name='label_reshape')
+            hard = cfg.TRAIN.get('ENABLE_OHEM', False)
+            if not hard:
+                label = mx.symbol.Reshape(data=label, shape=(-1,), name='label_reshape')
             fc2 = self._head(last_fm, rois)
             cls_score = mx.sym.FullyConnected(name='cls_score', data=fc2, num_hidden=num_classes)
             bbox_pred = mx.sym.FullyConnected(name='bbox_pred', data=fc2, num_hidden=4)
+            box_norm = 188.0 * B
+            if hard:   # the mined label / weight replace MultiProposalTarget's in both losses and in the label output
+                label, bbox_weight, k = self.ohem(cfg, cls_score, bbox_pred, label, bbox_target, bbox_weight, num_classes)
+                box_norm = float(k * B)
             cls_prob = mx.sym.SoftmaxOutput(name='cls_prob', data=cls_score, label=label, use_ignore=True, ignore_label=-1,
                                             grad_scale=grad_scale / (300.0 * B))
             bbox_loss_ = bbox_weight * mx.sym.smooth_l1(name='bbox_loss_', scalar=1.0, data=(bbox_pred - bbox_target))
-            bbox_loss = mx.sym.MakeLoss(name='bbox_loss', data=bbox_loss_, grad_scale=grad_scale / (188.0 * B))
+            bbox_loss = mx.sym.MakeLoss(name='bbox_loss', data=bbox_loss_, grad_scale=grad_scale / box_norm)
             cls_prob = mx.sym.Reshape(data=cls_prob, shape=(B, -1, num_classes), name='cls_prob_reshape')
             bbox_loss = mx.sym.Reshape(data=bbox_loss, shape=(B, -1, 4), name='bbox_loss_reshape')
             rpn_bbox_loss_ = rpn_bbox_weight * mx.sym.smooth_l1(name='rpn_bbox_loss_', scalar=1.0,

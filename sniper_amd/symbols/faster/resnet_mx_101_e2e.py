@@ -214,8 +214,14 @@ class resnet_mx_101_e2e(Symbol):
             rpn_prob, rpn_loss = self._rpn_losses(cfg, cls_r, box, label, target, weight)
             pt = self._proposal_target(cfg, rpn_prob, box, im_info, gt_boxes, valid_ranges)
             rois, rlabel, rtarget, rweight = pt[:4]
-            rlabel = mx.sym.Reshape(data=rlabel, shape=(-1,), name='label_reshape')
+            hard = cfg.TRAIN.get('ENABLE_OHEM', False)
+            if not hard:
+                rlabel = mx.sym.Reshape(data=rlabel, shape=(-1,), name='label_reshape')
             score, bpred = self._head(feat, rois, C)
+            box_norm = 188.0 * 16.0
+            if hard:   # the mined label / weight replace MultiProposalTarget's in both losses and in the label output
+                rlabel, rweight, k = self.ohem(cfg, score, bpred, rlabel, rtarget, rweight, C)
+                box_norm = float(k * cfg.TRAIN.BATCH_IMAGES)
             prob = mx.sym.SoftmaxOutput(name='cls_prob', data=score, label=rlabel, normalization='valid', use_ignore=True,
                                         ignore_label=-1, grad_scale=gs)
             outs = [rpn_prob, rpn_loss]
@@ -224,7 +230,7 @@ class resnet_mx_101_e2e(Symbol):
                 outs.append(mx.sym.SoftmaxOutput(name='cls_scale_prob', data=fr, label=scale_label, normalization='valid',
                                                  multi_output=True, use_ignore=True, ignore_label=-1, grad_scale=gs))
             l1 = rweight * mx.sym.smooth_l1(name='bbox_loss_', scalar=1.0, data=(bpred - rtarget))
-            bloss = mx.sym.MakeLoss(name='bbox_loss', data=l1, grad_scale=gs / (188.0 * 16.0))
+            bloss = mx.sym.MakeLoss(name='bbox_loss', data=l1, grad_scale=gs / box_norm)
             outs.append(mx.sym.Reshape(data=prob, shape=(cfg.TRAIN.BATCH_IMAGES, -1, C), name='cls_prob_reshape'))
             outs.append(mx.sym.Reshape(data=bloss, shape=(cfg.TRAIN.BATCH_IMAGES, -1, 4), name='bbox_loss_reshape'))
             outs.append(mx.sym.BlockGrad(rlabel))

@@ -36,14 +36,18 @@ class Trainer(object):
     (tests and tools/fix_bn_step.py train such a run at <= 2e-5).
     `fixed_params` replaces network.FIXED_PARAMS (None keeps the config's list): [] trains everything -- conv0, bn0 and stage 1
     included, through the max-pool backward -- except bn_data, which stays folded into the image packing whatever the list says
-    (MXNet would train bn_data_beta; that needs the stem's data gradient, which is never computed here)."""
+    (MXNet would train bn_data_beta; that needs the stem's data gradient, which is never computed here).
+    `ohem=k` trains with online hard example mining (TRAIN.ENABLE_OHEM = True, TRAIN.BATCH_ROIS_OHEM = k): per chip the k RoIs of
+    largest loss carry the R-CNN losses, on the device, inside the replayed step (None keeps the config's two keys)."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
-                 fix_bn=False, fixed_params=None):
+                 fix_bn=False, fixed_params=None, ohem=None):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
         if fixed_params is not None:
             cfg.network.FIXED_PARAMS = list(fixed_params)
+        if ohem is not None:
+            cfg.TRAIN.ENABLE_OHEM, cfg.TRAIN.BATCH_ROIS_OHEM = True, int(ohem)
         cfg.TRAIN.USE_NEG_CHIPS = n_proposals > 0
         np.random.seed(seed)
         self.roidb = make_roidb(n_images, seed=seed, n_proposals=n_proposals, with_masks=bool(cfg.TRAIN.WITH_MASK))
