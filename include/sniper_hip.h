@@ -37,9 +37,11 @@ int sn_version(void);
 const char *sn_last_error(void); /* thread-local text of the last failure */
 /* Test switch (process-wide, atomic; no reference counterpart): "proposal_full_sort" = 1 orders the proposals with the
  * general global-memory bitonic sort instead of radix select + LDS sort, "nms_full_mask" = 1 runs the full bitmask + scan
- * instead of the lazy kernel, "conv_no_persist" = 1 gives every convolution workgroup one output tile (no persistent tile loop).  Results are
- * identical either way (that is what the tests use it for; environment spellings, read once at load: SNIPER_FULL_SORT,
- * SNIPER_NMS_FULL, SNIPER_CONV_NO_PERSIST).  Any other name is an error. */
+ * instead of the lazy kernel, "conv_no_persist" = 1 gives every convolution workgroup one output tile (no persistent tile loop),
+ * "softmax_strided" = 1 sends the inner == 1 calls of sn_softmax_fwd / sn_softmax_output_bwd down the one-thread-per-position
+ * kernels instead of the row-block kernels.  Results are identical either way (that is what the tests use it for; environment
+ * spellings, read once at load: SNIPER_FULL_SORT, SNIPER_NMS_FULL, SNIPER_CONV_NO_PERSIST, SNIPER_SOFTMAX_STRIDED).  Any other
+ * name is an error. */
 int sn_debug_option(const char *name, int value);
 
 /* ------------------------------------------------------------------ box geometry ------------- */

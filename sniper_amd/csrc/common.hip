@@ -38,8 +38,8 @@ hipError_t sn_once_per_device_max_lds(const void *kernel, int bytes) {
 }
 
 static std::atomic<int> g_debug[SN_OPT_COUNT];
-static const char *const kDebugNames[SN_OPT_COUNT] = {"proposal_full_sort", "nms_full_mask", "conv_no_persist"};
-static const char *const kDebugEnv[SN_OPT_COUNT] = {"SNIPER_FULL_SORT", "SNIPER_NMS_FULL", "SNIPER_CONV_NO_PERSIST"};
+static const char *const kDebugNames[SN_OPT_COUNT] = {"proposal_full_sort", "nms_full_mask", "conv_no_persist", "softmax_strided"};
+static const char *const kDebugEnv[SN_OPT_COUNT] = {"SNIPER_FULL_SORT", "SNIPER_NMS_FULL", "SNIPER_CONV_NO_PERSIST", "SNIPER_SOFTMAX_STRIDED"};
 namespace {
 struct DebugInit {
   DebugInit() {

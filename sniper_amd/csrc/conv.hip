@@ -221,24 +221,33 @@ SN_EXPORT int sn_conv_dgrad_by_class(int on) {
   return SN_OK;
 }
 
-static ConvPlan conv_plan(const ConvParams &p, bool dgrad, int use_cfg = -1) {
-  // Layers whose taps are whole 64-channel K-steps and 16-byte addressable take a pipelined kernel; narrow outputs
-  // (stage1 / RPN heads) and the packed stem stay on conv_igemm_kernel.
+static ConvPlan conv_plan(const ConvParams &p, bool dgrad, int use_cfg = -1, bool ragged_ok = false) {
+  // Layers whose taps are 16-byte addressable take a pipelined kernel: rows of in_ps % 8 == 0 halves, taps of Cin % 8 == 0 channels
+  // (so that every tap of a weight row starts 16-byte aligned too).  A tap is ceil(Cin / 64) K-steps; when the last one is partial
+  // (Cin % 64 != 0: data gradients of the 72-channel offset layers and of the RPN / R-CNN heads) the launch runs a RAGGED
+  // instantiation (conv_dma_ragged.hip), which zero-fills the chunks beyond Cin.  Narrow outputs (stage 1, the forward heads), rows
+  // that are not 16-byte addressable (a 42-channel map of pixel stride 42) and the packed stem stay on conv_igemm_kernel.
+  // `ragged_ok`: only the plain launches (sn_conv_fwd, sn_conv_dgrad) plan a ragged contraction.  The queries the lowering chooses
+  // its entry points by (sn_conv_fwd_stats_blocks, sn_conv_dgrad_bn_blocks, sn_conv_fwd_dual_ok, the split-K workspace) answer for
+  // such layers what they always did, so no network's call sequence changes (tests/test_engine_call_trace.py).
   ConvPlan q = {0, 0, 0, 0, 0u, 0u, 0, 0};
   const unsigned long x_bytes = ((unsigned long)p.N * p.H * p.W - 1) * p.in_ps * 2 + (unsigned long)p.Cin * 2;
   const unsigned long w_bytes = (unsigned long)p.Nout * p.KH * p.KW * p.Cin * 2;
   // (Nout == 64 -- the stage-1 reductions and 3 x 3 layers, 327 680 pixels each -- stays on conv_igemm_kernel: the pipelined 64 x 128
   //  tile with half of its columns zero-filled made no difference to the step, profiles/r06_ab_nout64.txt; that option was removed)
-  if (p.Nout >= 65 && p.Cin % 64 == 0 && p.in_ps % 8 == 0 && x_bytes <= 0xFFFFFF00ul && w_bytes <= 0xFFFFFF00ul) {
+  const bool ragged = p.Cin % 64 != 0;
+  const int kpt = (p.Cin + 63) / 64;
+  if (p.Nout >= 65 && (ragged ? ragged_ok && p.Cin % 8 == 0 : true) && p.in_ps % 8 == 0 && x_bytes <= 0xFFFFFF00ul && w_bytes <= 0xFFFFFF00ul) {
     q.x_bytes = (unsigned)x_bytes;
     q.w_bytes = (unsigned)w_bytes;
     const int forced = g_conv_cfg.load(std::memory_order_relaxed);
     // a stride-2 data gradient walks its destination pixels parity class by parity class (each class only its own taps)
     const bool by_class = dgrad && p.stride == 2 && p.dil == 1 && p.Ho % 2 == 0 && p.Wo % 2 == 0 &&
                           g_dgrad_by_class.load(std::memory_order_relaxed) != 0;
-    const int nk_full = p.KH * p.KW * (p.Cin / 64);
-    const int nk = by_class ? std::max(1, ((p.KH + 1) / 2) * ((p.KW + 1) / 2) * (p.Cin / 64)) : nk_full;    // the busiest class
+    const int nk_full = p.KH * p.KW * kpt;
+    const int nk = by_class ? std::max(1, ((p.KH + 1) / 2) * ((p.KW + 1) / 2) * kpt) : nk_full;    // the busiest class
     int cfg = use_cfg > 0 ? use_cfg : (forced >= 0 ? forced : conv_dma_choice_balanced(p.M, p.Nout, nk, dgrad));
+    if (ragged && cfg > 0) cfg = conv_dma_ragged_cfg(cfg, dgrad);      // (only 6 / 14 / 16 are instantiated RAGGED; never persistent)
     if (by_class && cfg == 18 && use_cfg <= 0 && forced < 0) cfg = 16;      // (the specialised kernel carries no class arithmetic: conv_dma.hip kClassOk)
     // the persistent twins (24 / 26) of the 160 x 128 configurations: launches of >= 4 whole tiles per CU that divide over the 512
     // resident workgroups, short contractions (what a tile pays outside its K loop is what the persistent loop overlaps)
@@ -248,7 +257,7 @@ static ConvPlan conv_plan(const ConvParams &p, bool dgrad, int use_cfg = -1) {
     // (and 1 x 1, stride 1, unpadded: the persistent kernel addresses a row's source pixel as the row itself)
     const bool may_persist = !by_class && p.ksplit <= 1 && rows16 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 &&
                              conv_persist_tiles_per_wg(p.M, p.Nout, 160, 128) > 0;
-    if (use_cfg <= 0 && forced < 0 && (cfg == 14 || cfg == 16) && may_persist && nk >= 2 && nk <= 16 && sn_debug_get(SN_OPT_CONV_NO_PERSIST) == 0)
+    if (use_cfg <= 0 && forced < 0 && !ragged && (cfg == 14 || cfg == 16) && may_persist && nk >= 2 && nk <= 16 && sn_debug_get(SN_OPT_CONV_NO_PERSIST) == 0)
       cfg += 10;
     if ((cfg == 24 || cfg == 26) && (!may_persist || nk < 2)) cfg -= 10;      // forced on a launch that does not qualify: the plain twin
     if (cfg > 0) {
@@ -268,7 +277,7 @@ static ConvPlan conv_plan(const ConvParams &p, bool dgrad, int use_cfg = -1) {
 
 template <bool DGRAD>
 static int conv_launch(const ConvParams &p, hipStream_t s, int use_cfg = -1) {
-  const ConvPlan pl = conv_plan(p, DGRAD, use_cfg);
+  const ConvPlan pl = conv_plan(p, DGRAD, use_cfg, !p.stats && !p.out2 && p.ksplit <= 1);
   if (pl.dma) {
     ConvParams q = p;
     q.x_bytes = pl.x_bytes;

@@ -99,6 +99,9 @@ constexpr int kConvDmaConfigs = 26;    // highest configuration number (the tabl
 ConvDmaConfig conv_dma_config(int cfg);
 int conv_dma_launch(const ConvParams &p, bool dgrad, int cfg, hipStream_t s);
 void conv_dma_set_trace(unsigned long long *buf);
+// launches with Cin % 64 != 0 (conv_dma_ragged.hip): the configuration that runs in place of `cfg`, and the launch
+int conv_dma_ragged_cfg(int cfg, bool dgrad);
+int conv_dma_ragged_launch(const ConvParams &p, bool dgrad, int cfg, hipStream_t s);
 
 // ---- weight gradient (conv.hip: gather kernel for unaligned operands and the packed stem; conv_wgrad_ps.hip: everything else)
 struct WgradParams {

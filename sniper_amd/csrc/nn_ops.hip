@@ -1185,6 +1185,8 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float *__restric
   }
 }
 
+// exact count of the labels != ignore: the workgroup's four wave sums meet in LDS and ONE atomicAdd per workgroup leaves it (one per
+// wave over the 430 080 RPN labels was 6720 same-address atomics, serialised: 35 us for a 1.7 MB read; the launcher caps the grid)
 __global__ __launch_bounds__(256) void count_valid_kernel(const float *__restrict__ label, long n, float ignore,
                                                           int *__restrict__ count) {
   int c = 0;
@@ -1192,7 +1194,13 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const float *__restric
     c += (label[i] != ignore);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+  __shared__ int wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (t) atomicAdd(count, t);
+  }
 }
 
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float *__restrict__ p, const float *__restrict__ label,
@@ -1217,9 +1225,118 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float *__restric
   }
 }
 
+// ---- inner == 1 (the R-CNN classifier: 6000 rows of 81): with one thread per row the kernels above read and write with a stride
+// of K floats between neighbouring lanes (324 B: every access its own cache line, 170-250 GB/s).  Here a workgroup owns a block of
+// R consecutive rows, i.e. one contiguous range of memory: 16-byte coalesced loads bring it into LDS (row pitch K | 1 floats, odd,
+// so that the lanes of the row pass hit different banks), thread r runs THE SAME statements in the same order as softmax_fwd_kernel
+// over its row in LDS -- the result is bit-identical, tests/test_gpu_softmax_rows.py -- and the block goes back out coalesced.
+// R is a multiple of 4 (every block starts 16-byte aligned) and at most 64 (6000 rows -> 94 workgroups).
+constexpr int kSoftmaxRowsMax = 64, kSoftmaxLdsFloats = 16384;      // 64 KB of LDS at most
+static int softmax_rows_per_block(int K) { return std::min(kSoftmaxRowsMax, kSoftmaxLdsFloats / (K | 1)) & ~3; }
+// the row path: contiguous rows, a block of at least 16 of them in LDS (K <= 1023), 16-byte aligned tensors
+static bool softmax_rows_ok(const void *a, const void *b, int K, long inner) {
+  return inner == 1 && softmax_rows_per_block(K) >= 16 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 &&
+         sn_debug_get(SN_OPT_SOFTMAX_STRIDED) == 0;
+}
+
+__global__ __launch_bounds__(256) void softmax_rows_fwd_kernel(const float *__restrict__ x, float *__restrict__ p, long outer, int K,
+                                                               int R, SnDiv dK) {
+  extern __shared__ float sm_rows[];
+  const int KP = K | 1;
+  const long row0 = (long)blockIdx.x * R;
+  const int nr = (int)(outer - row0 < R ? outer - row0 : R);
+  const int n = nr * K, n4 = n >> 2;
+  const float *xb = x + row0 * K;
+  float *pb = p + row0 * K;
+  for (int v = threadIdx.x; v < n4; v += 256) {
+    const float4 f = reinterpret_cast<const float4 *>(xb)[v];
+    const float e[4] = {f.x, f.y, f.z, f.w};
+    unsigned k, r = sn_divmod(4u * v, dK, k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sm_rows[r * KP + k] = e[j];
+      if (++k == (unsigned)K) { k = 0; ++r; }
+    }
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) {
+    unsigned k, r = sn_divmod((unsigned)i, dK, k);
+    sm_rows[r * KP + k] = xb[i];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nr) {
+    float *xi = sm_rows + threadIdx.x * KP;
+    float m = xi[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, xi[k]);
+    float z = 0.f;
+    for (int k = 0; k < K; ++k) z += expf(xi[k] - m);
+    const float iz = 1.f / z;
+    for (int k = 0; k < K; ++k) xi[k] = expf(xi[k] - m) * iz;
+  }
+  __syncthreads();
+  for (int v = threadIdx.x; v < n4; v += 256) {
+    float e[4];
+    unsigned k, r = sn_divmod(4u * v, dK, k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      e[j] = sm_rows[r * KP + k];
+      if (++k == (unsigned)K) { k = 0; ++r; }
+    }
+    reinterpret_cast<float4 *>(pb)[v] = make_float4(e[0], e[1], e[2], e[3]);
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) {
+    unsigned k, r = sn_divmod((unsigned)i, dK, k);
+    pb[i] = sm_rows[r * KP + k];
+  }
+}
+
+// the gradient is elementwise given p, the row's label and the count: the same row blocks, 16 bytes per lane, no LDS
+__global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float *__restrict__ p, const float *__restrict__ label,
+                                                               float *__restrict__ g, long outer, int K, int R, SnDiv dK, float ignore,
+                                                               int use_ignore, float grad_scale, int normalize_valid,
+                                                               const int *__restrict__ valid_count) {
+  float mul = grad_scale;
+  if (normalize_valid) {
+    const int vc = *valid_count;
+    mul = grad_scale / (float)(vc > 1 ? vc : 1);
+  }
+  const long row0 = (long)blockIdx.x * R;
+  const int nr = (int)(outer - row0 < R ? outer - row0 : R);
+  const int n = nr * K, n4 = n >> 2;
+  const float *pb = p + row0 * K, *lb = label + row0;
+  float *gb = g + row0 * K;
+  auto one = [&](float pv, unsigned r, unsigned k) {
+    const float l = lb[r];
+    const bool ign = use_ignore && l == ignore;
+    const int li = (int)l;
+    return ign ? 0.f : mul * (pv - ((int)k == li ? 1.f : 0.f));
+  };
+  for (int v = threadIdx.x; v < n4; v += 256) {
+    const float4 f = reinterpret_cast<const float4 *>(pb)[v];
+    float e[4] = {f.x, f.y, f.z, f.w};
+    unsigned k, r = sn_divmod(4u * v, dK, k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      e[j] = one(e[j], r, k);
+      if (++k == (unsigned)K) { k = 0; ++r; }
+    }
+    reinterpret_cast<float4 *>(gb)[v] = make_float4(e[0], e[1], e[2], e[3]);
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) {
+    unsigned k, r = sn_divmod((unsigned)i, dK, k);
+    gb[i] = one(pb[i], r, k);
+  }
+}
+
 SN_EXPORT int sn_softmax_fwd(const float *x, float *p, long outer, int K, long inner, sn_stream_t stream) {
   SN_REQUIRE(x && p && outer > 0 && K > 0 && inner > 0, "sn_softmax_fwd: bad arguments");
-  hipLaunchKernelGGL(softmax_fwd_kernel, dim3(ew_blocks(outer * inner)), dim3(256), 0, sn_stream(stream), x, p, outer, K, inner);
+  if (softmax_rows_ok(x, p, K, inner)) {
+    const int R = softmax_rows_per_block(K);
+    SN_REQUIRE((outer + R - 1) / R < (1l << 31), "sn_softmax_fwd: too many rows");
+    hipLaunchKernelGGL(softmax_rows_fwd_kernel, dim3((unsigned)((outer + R - 1) / R)), dim3(256), (size_t)R * (K | 1) * sizeof(float),
+                       sn_stream(stream), x, p, outer, K, R, sn_div_make((unsigned)K));
+  } else {
+    hipLaunchKernelGGL(softmax_fwd_kernel, dim3(ew_blocks(outer * inner)), dim3(256), 0, sn_stream(stream), x, p, outer, K, inner);
+  }
   SN_CHECK_LAUNCH();
   return SN_OK;
 }
@@ -1232,12 +1349,19 @@ SN_EXPORT int sn_softmax_output_bwd(const float *p, const float *label, float *g
   hipStream_t s = sn_stream(stream);
   if (normalize_valid) {
     SN_HIP(hipMemsetAsync(ws, 0, sizeof(int), s));
-    hipLaunchKernelGGL(count_valid_kernel, dim3(ew_blocks(outer * inner)), dim3(256), 0, s, label, outer * inner,
+    hipLaunchKernelGGL(count_valid_kernel, dim3(sn_blocks(outer * inner, 256)), dim3(256), 0, s, label, outer * inner,
                        use_ignore ? ignore_label : -1e30f, ws);
     SN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(ew_blocks(outer * inner)), dim3(256), 0, s, p, label, grad, outer, K, inner,
-                     ignore_label, use_ignore, grad_scale, normalize_valid, ws);
+  if (softmax_rows_ok(p, grad, K, inner)) {
+    const int R = softmax_rows_per_block(K);
+    SN_REQUIRE((outer + R - 1) / R < (1l << 31), "sn_softmax_output_bwd: too many rows");
+    hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3((unsigned)((outer + R - 1) / R)), dim3(256), 0, s, p, label, grad, outer, K, R,
+                       sn_div_make((unsigned)K), ignore_label, use_ignore, grad_scale, normalize_valid, ws);
+  } else {
+    hipLaunchKernelGGL(softmax_bwd_kernel, dim3(ew_blocks(outer * inner)), dim3(256), 0, s, p, label, grad, outer, K, inner,
+                       ignore_label, use_ignore, grad_scale, normalize_valid, ws);
+  }
   SN_CHECK_LAUNCH();
   return SN_OK;
 }
