@@ -276,7 +276,8 @@ int sn_conv_dgrad_bn(const void *dy, const void *wt, const void *accumulate, voi
                      float *partials, sn_stream_t stream);
 /* Weight gradient, accumulated (+=) into dw fp32 [Cout][KH*KW][Cin].  Layers whose weight tensor is small relative to
  * the pixel count are split over K; with ws = sn_conv_wgrad_workspace_bytes(...) bytes of scratch the partials are
- * reduced without atomics (deterministic); ws may be NULL (atomic accumulation). */
+ * reduced in split order without atomics (deterministic).  ws may be NULL, or smaller than the query: the layer then
+ * runs unsplit, one owner per dw element -- slower, still no atomics, the same sums in another order. */
 size_t sn_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int x_pix_stride, int Cout, int dy_pix_stride, int KH, int KW,
                                      int stride, int pad, int dil);
 int sn_conv_wgrad(const void *dy, const void *x, float *dw, int N, int H, int W, int Cin, int x_pix_stride, int Cout,

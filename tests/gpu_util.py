@@ -97,3 +97,24 @@ def assert_close(got, want, rtol, atol, what='', sig_rtol=None):
         assert p999 <= lim, ("%s: relative error of the significant elements (>= 5%% of max|want| = %.4g): p99.9 %.3g > %.3g "
                              "(p50 %.3g, p99 %.3g, max %.3g)" % (what, q['max_abs_want'], p999, lim, q['rel_significant']['p50'],
                                                                  q['rel_significant']['p99'], q['rel_significant']['p100']))
+
+
+class Stamps:
+    """did the next launches run the pipelined convolution kernel?  (its workgroups stamp their phases into the trace buffer of
+    sn_conv_trace; conv_igemm_kernel writes none)"""
+
+    def __init__(self, words=1 << 20):
+        self.buf = torch.zeros(words, dtype=torch.int64, device=dev())      # a launch stamps 8 words per workgroup
+
+    def __enter__(self):
+        from sniper_amd import hip
+        self.buf.zero_()
+        torch.cuda.synchronize()
+        hip.call('sn_conv_trace', self.buf)
+        return self
+
+    def __exit__(self, *exc):
+        from sniper_amd import hip
+        torch.cuda.synchronize()
+        hip.call('sn_conv_trace', None)
+        self.pipelined = bool((self.buf != 0).any().item())

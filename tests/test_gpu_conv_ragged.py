@@ -12,7 +12,7 @@ import torch.nn.functional as Fnn
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import assert_close, dev, f16r, from_nhwc, to_nhwc_f16, w_to_otI  # noqa: E402
+from gpu_util import Stamps as _Stamps, assert_close, dev, f16r, from_nhwc, to_nhwc_f16, w_to_otI  # noqa: E402
 
 # name -> N, H, W (of dx), dx channels, contraction (= dy channels), K, stride, pad, dilation
 CASES = {
@@ -54,24 +54,6 @@ def _problem(name):
     for a in (w, dy, want):
         a.setflags(write=False)
     return dy, w, want
-
-
-class _Stamps:
-    """did the next launches run the pipelined kernel?  (its workgroups stamp their phases into the trace buffer)"""
-
-    def __init__(self):
-        self.buf = torch.zeros(1 << 20, dtype=torch.int64, device=dev())
-
-    def __enter__(self):
-        self.buf.zero_()
-        torch.cuda.synchronize()
-        _hip().call('sn_conv_trace', self.buf)
-        return self
-
-    def __exit__(self, *exc):
-        torch.cuda.synchronize()
-        _hip().call('sn_conv_trace', None)
-        self.pipelined = bool((self.buf != 0).any().item())
 
 
 def _dgrad(name, dy_ps=None, spare=0.0):
