@@ -377,6 +377,24 @@ int sn_gconv_dgrad(const void *dy, const void *w, const void *accumulate, void *
 size_t sn_gconv_wgrad_workspace_bytes(int N, int H, int W, int C, int O, int groups, int KH, int KW, int stride, int pad, int dil);
 int sn_gconv_wgrad(const void *dy, const void *x, float *dw, int N, int H, int W, int C, int O, int dy_pix_stride, int x_pix_stride,
                    int groups, int KH, int KW, int stride, int pad, int dil, void *ws, size_t ws_bytes, sn_stream_t stream);
+/* Grouped deformable convolution (DeformableConvolution with num_group > 1; the ResNeXt stage-4 3x3 with num_group = 64,
+ * num_deformable_group = 4), channels-last fp16 with pixel pitches, fp32 accumulation, compact [O][9][C/groups] fp16 weights.
+ * The bilinear sample of sn_deform_im2col is taken in registers and fed to the matrix cores: no column buffer in the forward pass
+ * or the weight gradient.  offset (N,Ho,Wo,>=2*9*deformable_groups) with its pixel pitch, offset_dtype 0 = fp16, 1 = fp32.
+ * One path only -- C/groups == O/groups in {4, 8, 16, 32}, C % 32 == 0, (C / deformable_groups) % 32 == 0, a 3x3 kernel, square
+ * stride >= 1 / pad / dilation; anything else (groups == 1 included) is an argument error naming the condition.
+ * fwd: bias fp32 [O] or NULL, optional ReLU.  dcol (M, 9, C) fp16 = sum_o dy[m][o] * w[o][t][ci], the input of sn_deform_col2im
+ * (which needs M * 9 * C < 2^31).  wgrad accumulates (+=) into fp32 dw [O][9][C/groups] through per-block partials in `ws` summed
+ * in block order (deterministic, no atomics). */
+int sn_gdeform_fwd(const void *x, const void *offset, const void *w, const float *bias, void *y, int N, int H, int W, int C,
+                   int in_pix_stride, int O, int out_pix_stride, int groups, int deformable_groups, int KH, int KW, int stride, int pad,
+                   int dil, int offset_pix_stride, int offset_dtype, int relu, sn_stream_t stream);
+int sn_gdeform_dcol(const void *dy, const void *w, void *dcol, int N, int H, int W, int C, int O, int dy_pix_stride, int groups, int KH,
+                    int KW, int stride, int pad, int dil, sn_stream_t stream);
+size_t sn_gdeform_wgrad_workspace_bytes(int N, int H, int W, int C, int O, int groups, int KH, int KW, int stride, int pad, int dil);
+int sn_gdeform_wgrad(const void *dy, const void *x, const void *offset, float *dw, int N, int H, int W, int C, int O,
+                     int dy_pix_stride, int x_pix_stride, int groups, int deformable_groups, int KH, int KW, int stride, int pad,
+                     int dil, int offset_pix_stride, int offset_dtype, void *ws, size_t ws_bytes, sn_stream_t stream);
 /* clip(lo, hi) (mx.sym.clip; relu6) forward, or backward = (lo <= ref <= hi ? a : 0) [+ accumulate]. */
 int sn_clip_f16(const void *a, const void *ref, const void *accumulate, void *y, long rows, int C, int ps_a, int ps_ref, int ps_acc,
                 int ps_y, float lo, float hi, int backward, sn_stream_t stream);

@@ -99,6 +99,14 @@ def resnext101_e2e(batch_images=20):
     return c
 
 
+def resnext101_e2e_dcn(batch_images=20):
+    """resnext101_e2e with the reference's deformable stage 4 (symbols/faster/resnext_mx_101_e2e_dcn.py,
+    symbols/faster/resnext_mx_101.py:129-198): grouped deformable 3x3 convolutions with learned offsets."""
+    c = res101_e2e(batch_images)
+    c.symbol = 'resnext_mx_101_e2e_dcn'
+    return c
+
+
 def res101_e2e_autofocus(batch_images=20):
     """configs/faster/sniper_res101_e2e_autofocus.yml TEST section (BASELINE C5): coarse-to-fine scales, FocusChips."""
     c = res101_e2e(batch_images)

@@ -15,6 +15,7 @@
 // workspace; sn_partial_sum (common.hip) adds the slabs to dw in block order (no atomics: the same bits every run).
 // Everything else (Cg != Og, other widths, other kernel sizes, fp32 output) takes the plain kernels at the end of the file.
 #include "conv_common.h"
+#include "gconv_slab.h"
 
 struct GconvParams {
   int N, H, W, Ho, Wo;        // input and output extents of the CONVOLUTION (the data gradient reads Ho x Wo, writes H x W)
@@ -113,12 +114,6 @@ __global__ __launch_bounds__(256) void gconv_mfma_kernel(const half_t *__restric
 // ---------------------------------------------------------------------------------------------------------------------------------
 // weight gradient on the matrix cores: D[o][ci] += sum over 32 pixels dyT[o][pix] * xT[ci][pix] per tap
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int kTP = 40;       // halfs per row of a [32 pixels][32 channels] LDS image (80 B: 16-byte aligned rows)
-
-// tr_frag (conv_common.h) on these images: rows = pixels 8q + {0..3} and 8q + {4..7} -- the second read is 4 rows down -- columns =
-// the 16 channels of a block: lane (r, q) receives channel r of pixels 8q .. 8q + 7.
-constexpr int kTrSecond = 4 * kTP;
-
 // NB = 1: Cg <= 16, only the two diagonal 16 x 16 blocks of a slab hold weights;  NB = 2: Cg == 32, all four
 template <int T, int NB>
 __global__ __launch_bounds__(256) void gconv_wgrad_mfma_kernel(const half_t *__restrict__ dy, const half_t *__restrict__ x,
@@ -338,8 +333,6 @@ static bool gc_fast(const GconvParams &p) {
   return p.Cg == p.Og && (p.Cg == 4 || p.Cg == 8 || p.Cg == 16 || p.Cg == 32) && p.C % 32 == 0 && p.KH == p.KW && (T == 1 || T == 9) &&
          (p.stride == 1 || p.stride == 2);
 }
-// waves per workgroup: every wave of a workgroup owns a slab that exists
-static int gc_waves(int nslab) { return nslab % 4 == 0 ? 4 : (nslab % 2 == 0 ? 2 : 1); }
 static int gc_blocks(long total) { return sn_blocks(total, 16384); }
 
 template <bool DGRAD>
@@ -399,12 +392,7 @@ SN_EXPORT int sn_gconv_dgrad(const void *dy, const void *w, const void *accumula
 static int gc_wgrad_blocks(const GconvParams &p, int *per_block) {
   const long M = (long)p.N * p.Ho * p.Wo;
   if (gc_fast(p)) {
-    const int nslab = p.C / 32, gy = nslab / gc_waves(nslab);
-    const long chunks = (M + 31) / 32;
-    long blocks = sn_div_up(512, gy);               // about two workgroups per CU
-    if (blocks > chunks) blocks = chunks;
-    *per_block = (int)((chunks + blocks - 1) / blocks);
-    return (int)((chunks + *per_block - 1) / *per_block);
+    return gc_chunk_blocks(M, p.C / 32, per_block);
   }
   long blocks = (M + 63) / 64;
   if (blocks > 128) blocks = 128;

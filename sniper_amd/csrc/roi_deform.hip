@@ -8,6 +8,7 @@
 // channels, so each lane moves 16 bytes per corner and a wave covers 512 channels of one sample.
 // HBM-bound: DPSROIPool forward writes R*49*C*2 bytes and reads the (L2-resident) feature map.
 #include "common.h"
+#include "deform_sample.h"
 #include <type_traits>
 
 #include <stdlib.h>
@@ -1230,22 +1231,6 @@ SN_EXPORT int sn_psroi_pool_bwd(const void *dout, const void *data, const float 
 //   p = (oy*s - pad + kh*dil + dy,  ox*s - pad + kw*dil + dx);  zero unless 0 <= p < (H, W)
 //   low = floor(p); if low >= dim-1: high = low = dim-1, frac = 0; else high = low+1
 // ---------------------------------------------------------------------------------------------
-struct DeformSample {
-  bool ok;
-  int y0, y1, x0, x1;
-  float ly, lx;
-};
-
-__device__ __forceinline__ DeformSample deform_sample(float py, float px, int H, int W) {
-  DeformSample s;
-  s.ok = py >= 0.f && px >= 0.f && py < (float)H && px < (float)W;
-  s.y0 = (int)floorf(py);
-  s.x0 = (int)floorf(px);
-  if (s.y0 >= H - 1) { s.y0 = s.y1 = H - 1; s.ly = 0.f; } else { s.y1 = s.y0 + 1; s.ly = py - (float)s.y0; }
-  if (s.x0 >= W - 1) { s.x0 = s.x1 = W - 1; s.lx = 0.f; } else { s.x1 = s.x0 + 1; s.lx = px - (float)s.x0; }
-  return s;
-}
-
 template <typename TO>
 __global__ __launch_bounds__(256) void deform_im2col_kernel(const half_t *__restrict__ data, const TO *__restrict__ offset,
                                                             half_t *__restrict__ col, int N, int H, int W, int C, int Ho, int Wo,

@@ -739,7 +739,9 @@ class FullyConnectedStep(_GemmLike):
 
 @register('DeformableConvolution')
 class DeformableConvolutionStep(Step):
-    """DCN v1: bilinear gather into a (M, T*C) column buffer + 1x1 GEMM (call site :124-128)."""
+    """DCN v1: bilinear gather into a (M, T*C) column buffer + 1x1 GEMM (call site :124-128).  num_group > 1 (the ResNeXt stage 4,
+    resnext_mx_101.py:161-168): the fused slab kernels of gdeform.hip on the compact weights -- no column buffer, no transposed copy,
+    no split-K and none of the dense-only fusions."""
 
     def setup(self):
         ex, a = self.ex, self.a
@@ -748,25 +750,44 @@ class DeformableConvolutionStep(Step):
         self.k, self.s = _tup(a['kernel']), _tup(a.get('stride', (1, 1)))
         self.p, self.d = _tup(a.get('pad', (0, 0))), _tup(a.get('dilate', (1, 1)))
         self.dg = int(a.get('num_deformable_group', 1))
-        if int(a.get('num_group', 1)) > 1:
-            raise NotImplementedError('%s: DeformableConvolution with num_group=%s (grouped deformable convolution is not built)' %
-                                      (self.node.name, a.get('num_group')))
+        self.groups = int(a.get('num_group', 1))
         self.N, self.C, self.H, self.W = self.x.shape
         _, self.O, self.Ho, self.Wo = self.out_shape()
         self.T = self.k[0] * self.k[1]
-        self.w = ex.register_param(self.pname('weight'), 'conv', None, need_wT=ex.for_training)
+        if self.groups > 1:
+            self._require_slab_path()
+        # (grouped: (O, Cg, 3, 3) -> the compact [O][9][Cg] the grouped ConvolutionStep registers, read as it lies by all three kernels)
+        self.w = ex.register_param(self.pname('weight'), 'conv', None, need_wT=ex.for_training and self.groups == 1)
         self.b = ex.register_param(self.pname('bias')) if 'bias' in self.slots else None
         self.y = self.new_out('act')
         self.y.needs_grad = ex.for_training
-        self.col = ex.act_empty((self.N * self.Ho * self.Wo, self.T * self.C), F16)
+        self.col = ex.act_empty((self.N * self.Ho * self.Wo, self.T * self.C), F16) if self.groups == 1 else None
         self.wT_flat = None
         self.out_f32 = False              # (_fwd_splitk: the column GEMM writes fp16)
         self._splitk_bytes = None         # first test-time forward: scratch bytes of the column GEMM's split-K launch (0: not split)
         self.dws = None                   # first backward: max |offset| of the launch, prunes the data gradient's scan
 
+    def _require_slab_path(self):
+        """num_group > 1 runs on the 32-channel-slab matrix-core kernels or not at all (sn_gdeform_* refuse the same shapes)"""
+        g, cg = self.groups, self.C // self.groups
+        bad = None
+        if self.C % g or self.O % g or cg != self.O // g:
+            bad = 'C / num_group == O / num_group (got %d -> %d channels)' % (self.C, self.O)
+        elif cg not in (4, 8, 16, 32) or self.C % 32:
+            bad = 'C / num_group in {4, 8, 16, 32} and C %% 32 == 0 (got C = %d, C / num_group = %d)' % (self.C, cg)
+        elif self.C % self.dg or (self.C // self.dg) % 32:
+            bad = '(C / num_deformable_group) %% 32 == 0 (got %d / %d)' % (self.C, self.dg)
+        elif self.k != (3, 3):
+            bad = 'a 3x3 kernel (got %dx%d)' % self.k
+        elif not (self.s[0] == self.s[1] and self.p[0] == self.p[1] and self.d[0] == self.d[1]):
+            bad = 'square stride, pad and dilation'
+        if bad:
+            raise NotImplementedError('%s: DeformableConvolution with num_group=%d needs %s: grouped deformable convolution is built '
+                                      'for the matrix-core path only' % (self.node.name, g, bad))
+
     def transpose_jobs(self, only_trainable=False):
         """the deformable convolution's data gradient is a 1x1 GEMM over the (tap, channel) column: W^T as [T*C][O]"""
-        if not self.ex.for_training or (only_trainable and not self.w.trainable):
+        if self.groups > 1 or not self.ex.for_training or (only_trainable and not self.w.trainable):
             return []
         if self.wT_flat is None:
             self.wT_flat = self.ex.zeros((self.T * self.C, 1, _pad8(self.O)), F16)
@@ -776,6 +797,11 @@ class DeformableConvolutionStep(Step):
         ex = self.ex
         x, off = ex.as_act(self.x), ex.as_act(self.off)
         oc = self.off.shape[1]
+        if self.groups > 1:
+            hip.call('sn_gdeform_fwd', x, off, self.w.w16, self.b.master if self.b is not None else None, self.y.t, self.N, self.H,
+                     self.W, self.C, self.C, self.O, self.O, self.groups, self.dg, self.k[0], self.k[1], self.s[0], self.p[0],
+                     self.d[0], oc, 0, 0, hip.stream())
+            return
         hip.call('sn_deform_im2col', x, off, self.col, self.N, self.H, self.W, self.C, self.k[0], self.k[1], self.s[0], self.p[0],
                  self.d[0], self.dg, oc, 0, hip.stream())
         M, K = self.col.shape
@@ -790,11 +816,18 @@ class DeformableConvolutionStep(Step):
         if self.y.grad is None:
             return
         dy = self.y.grad
-        M, K = self.col.shape
+        M, K = self.N * self.Ho * self.Wo, self.T * self.C
         Op = _pad8(self.O)
         assert Op == self.O
+        oc = self.off.shape[1]
+        geom = (self.k[0], self.k[1], self.s[0], self.p[0], self.d[0])
         def param_grads():
-            if self.w.trainable:
+            if self.w.trainable and self.groups > 1:
+                # re-samples x: per layer through the shared scratch like the grouped convolution's, not a row of the batched tables
+                need = hip.query('sn_gdeform_wgrad_workspace_bytes', self.N, self.H, self.W, self.C, self.O, self.groups, *geom)
+                hip.call('sn_gdeform_wgrad', dy, ex.as_act(self.x), ex.as_act(self.off), self.w.grad, self.N, self.H, self.W, self.C,
+                         self.O, Op, self.C, self.groups, self.dg, *geom, oc, 0, ex.ws.get(need), need, hip.stream())
+            elif self.w.trainable:
                 _wgrad(ex, dy, self.col, self.w.grad, M, 1, 1, K, K, self.O, Op, 1, 1, 1, 0, 1)
             if self.b is not None and self.b.trainable:
                 _bias_grad(ex, dy, self.b.grad, M, self.O, Op)
@@ -802,8 +835,11 @@ class DeformableConvolutionStep(Step):
             ex.on_side(param_grads, keep=(dy,))
         if self.x.needs_grad or self.off.needs_grad:
             dcol = ex.empty((M, K), F16)
-            hip.call('sn_conv_dgrad', dy, self.wT_flat, None, dcol, M, 1, 1, K, K, Op, Op, K, 1, 1, 1, 0, 1, 0, hip.stream())
-            oc = self.off.shape[1]
+            if self.groups > 1:
+                hip.call('sn_gdeform_dcol', dy, self.w.w16, dcol, self.N, self.H, self.W, self.C, self.O, Op, self.groups, *geom,
+                         hip.stream())
+            else:
+                hip.call('sn_conv_dgrad', dy, self.wT_flat, None, dcol, M, 1, 1, K, K, Op, Op, K, 1, 1, 1, 0, 1, 0, hip.stream())
             d16 = ex.empty((self.N, self.H, self.W, self.C), F16) if self.x.needs_grad else None
             d_off = ex.empty((self.N, self.Ho, self.Wo, oc), F16) if self.off.needs_grad else None
             if self.dws is None:

@@ -9,8 +9,8 @@ head initialisation of resnet_mx_101_e2e.py.
 Deviations from the reference file, which is dead upstream (no config names it, it imports a module that does not exist and its
 test graph uses an undefined name), so the mirror is "its trunk under our e2e heads":
   * stage 4 is three units with a grouped DILATION-2 3x3 conv2 (stride 1, pad 2), what resnetc5(deform=False) builds for the dense
-    trunk; the reference's stage 4 is a grouped deformable convolution (:161-168), which the engine does not build.  The weight
-    shape (2048, 32, 3, 3) is the reference's.
+    trunk; the reference's stage 4 is a grouped deformable convolution (:161-168): resnext_mx_101_e2e_dcn.py builds that one.  The
+    weight shape (2048, 32, 3, 3) is the reference's.
   * the shortcut BatchNorm's statistics mode follows its unit (moving statistics in the frozen stage 1 and under fix_bn, batch
     statistics otherwise); the reference has the two branches swapped at :119-122.
 """
@@ -29,7 +29,7 @@ class resnext_mx_101_e2e(base.resnet_mx_101_e2e):
 
     def _unit(self, x, nf, stride, dim_match, name, frozen=False, deform=False, dilate=False):
         if deform:
-            raise NotImplementedError('%s: grouped deformable convolution is not built' % name)
+            raise NotImplementedError('%s: the deformable stage 4 is resnext_mx_101_e2e_dcn' % name)
         mid = int(nf * self.MID)
         c1 = self._conv(x, name + '_conv1', mid, 1)
         a1 = self._bn_relu(c1, name, 1, frozen)
