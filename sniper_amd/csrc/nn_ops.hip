@@ -70,11 +70,14 @@ __device__ __forceinline__ bool bn_act_pass(float y, int act) {
 }
 
 // The per-channel coefficients and the per-element forms, spelled with explicit roundings: the values do not depend on what the
-// compiler would contract in the kernel that computes them.
+// compiler would contract in the kernel that computes them.  __fmul_rn / __fadd_rn / __fsub_rn are the plain operators in this
+// toolchain and ARE contracted (-ffp-contract=fast): a product never feeds one of them here -- every fused operation is an
+// __fmaf_rn.  (shift was spelled __fsub_rn(beta, __fmul_rn(., invstd)) and compiled to this fma: the value is unchanged, and
+// tests/test_gpu_bn_exact.py pins it on the bits.)
 __device__ __forceinline__ void bn_fwd_coefs(double mean, double var, float eps, float g, float beta, float &sc, float &sh, float &invstd) {
   invstd = (float)(1.0 / sqrt(var + (double)eps));
   sc = __fmul_rn(g, invstd);
-  sh = __fsub_rn(beta, __fmul_rn(__fmul_rn((float)mean, g), invstd));
+  sh = __fmaf_rn(-__fmul_rn((float)mean, g), invstd, beta);
 }
 __device__ __forceinline__ float bn_running(float run, float stat, float momentum) {
   return __fmaf_rn(run, momentum, __fmul_rn(stat, 1.f - momentum));
