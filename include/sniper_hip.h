@@ -456,6 +456,61 @@ int sn_box_annotator_ohem(const float *cls_score, const float *bbox_pred, const 
                           const float *bbox_weights, float *labels_ohem, float *bbox_weights_ohem, float *fg_labels /* or NULL */,
                           int B, int R, int C, int box_dim, int roi_per_img, sn_stream_t stream);
 
+/* COCO box evaluation (lib/dataset/pycocotools/cocoeval.py:163-272 evaluateImg, :312-365 accumulate; IoU = bbIou,
+ * lib/dataset/pycocotools/maskApi.c:98-109).  float64 and integer counts throughout: `precision` and `recall` are the reference's
+ * bits.  A PROBLEM is one (category, image) pair with at least one detection or one box; the P problems are stored category-major,
+ * then by image.  All tensors are device pointers except h_max_dets.
+ *   dt        (ND,6) f64   x, y, w, h, score, area, a problem's detections contiguous in arrival order;  dt_off (P+1) i32
+ *   gt        (NG,5) f64   x, y, w, h, area;  gt_flags (NG) u8, bit 0 = iscrowd, bit 1 = ignore;           gt_off (P+1) i32
+ *   kp_off    (P+1) i32    prefix sum of min(D_p, max_det): where a problem's KEPT detections sit in the NK-long outputs
+ *   cat_off   (K+1) i32    the first problem of every category (cat_off[k] == cat_off[k+1]: the category is absent)
+ *   iou_thrs (T) f64, area_rng (A,2) f64 (both bounds inclusive), rec_thrs (R) f64, h_max_dets (M) i32 in HOST memory.
+ * sn_coco_match, one launch, per problem: ranks the detections by descending score (equal scores by arrival order), keeps the first
+ * max_det, and runs the greedy matching of every (area range, threshold) over them:
+ *   dt_rank   (NK) i32      arrival index of the r-th kept detection
+ *   dt_match  (A,T,NK) i32  1 + arrival index (within the problem) of the matched box, 0 = unmatched
+ *   dt_ignore (A,T,NK) u8   the matched box is ignored, or the detection is unmatched and its area lies outside the range
+ *   gt_match  (A,T,NG) i32  1 + rank of the (last) detection that matched the box, 0 = unmatched
+ *   gt_ignore (A,NG) u8     iscrowd | ignore | area < lo | area > hi
+ * A detection qualifies for a box when IoU >= min(t, 1 - 1e-10); the best IoU wins, on equal IoU the LATER box; boxes that are not
+ * ignored and not matched are searched first, ignored boxes only if none of those qualifies, and an ignored box that is already
+ * matched is skipped unless it is a crowd.
+ * sn_coco_accumulate, three launches: precision (T,R,K,A,M) f64 and recall (T,K,A,M) f64, every element written (-1 where the
+ * category is absent or has no box that the area range keeps).  Detections of a category are ordered by (descending score, position
+ * in the concatenation of the problems) -- what a stable mergesort of -score yields.  From the first recall threshold whose
+ * searchsorted index is past the last detection onward, precision stays 0 (the reference's try/except).
+ * max_dt_per_problem, max_gt_per_problem, max_kept_per_category: the largest D_p, G_p and per-category kept count, which the caller
+ * knows from building the offsets; the first two are checked against the limits, the last sizes the ordering launch.
+ * Refused before any launch, by a message that names the condition: a NULL tensor; P < 1; T, A, M or R below 1 or above
+ * SN_COCO_MAX_T / _A / _M / _R; K above 65535; max_det < 1; max_dets not ascending or its last entry != max_det; a problem with more
+ * than SN_COCO_MAX_DT detections (their scores are ranked in LDS) or SN_COCO_MAX_GT boxes (four per lane, in registers); row counts
+ * past 32-bit indexing; a workspace shorter than sn_coco_accumulate_workspace_bytes(NK, T, A).  sn_coco_match needs no workspace
+ * (sn_coco_match_workspace_bytes() = 0).  sn_coco_limits: h_out8 (HOST) = {MAX_DT, MAX_GT, MAX_T, MAX_A, MAX_M, MAX_R, detections per
+ * workgroup of the ordering launch, detections per chunk of the scans}.
+ * No atomics, no host read-back, the same bits every run. */
+#define SN_COCO_MAX_DT 1024
+#define SN_COCO_MAX_GT 256
+#define SN_COCO_MAX_T 16
+#define SN_COCO_MAX_A 8
+#define SN_COCO_MAX_M 4
+#define SN_COCO_MAX_R 128
+int sn_coco_limits(int32_t *h_out8);
+/* Detections as the test run holds them, rows (x1, y1, x2, y2, score) float64 (rows_f32 = 0) or float32 (1), -> dt rows
+ * (x1, y1, x2 - x1 + 1, y2 - y1 + 1, score, w * h) float64 WITHOUT the rounding of the reference's result file; output row j reads
+ * input row src[j] (src (n) i32, or NULL for row j). */
+int sn_coco_pack_rows(const void *rows, int rows_f32, const int32_t *src, long n, double *dt6, sn_stream_t stream);
+size_t sn_coco_match_workspace_bytes(void);
+int sn_coco_match(const double *dt, const int32_t *dt_off, const int32_t *kp_off, const double *gt, const uint8_t *gt_flags,
+                  const int32_t *gt_off, const double *iou_thrs, const double *area_rng, int P, int T, int A, int max_det,
+                  int max_dt_per_problem, int max_gt_per_problem, long NK, long NG, int32_t *dt_rank, int32_t *dt_match,
+                  uint8_t *dt_ignore, int32_t *gt_match, uint8_t *gt_ignore, sn_stream_t stream);
+size_t sn_coco_accumulate_workspace_bytes(long NK, int T, int A);
+int sn_coco_accumulate(const double *dt, const int32_t *dt_off, const int32_t *kp_off, const int32_t *gt_off, const int32_t *cat_off,
+                       const int32_t *dt_rank, const int32_t *dt_match, const uint8_t *dt_ignore, const uint8_t *gt_ignore,
+                       const double *rec_thrs, const int32_t *h_max_dets, int P, int K, int T, int A, int M, int R, int max_det,
+                       int max_kept_per_category, long NK, long NG, void *ws, size_t ws_bytes, double *precision, double *recall,
+                       sn_stream_t stream);
+
 /* MultiProposal (:347-355) / MultiProposalTarget (:283-284).  cls_prob (B,2,A*Fh,Fw), bbox_pred (B,4A,Fh,Fw),
  * im_info (B,3), gt_boxes (B,G,5), valid_ranges (B,2), base_anchors (A,4): all fp32 device. */
 size_t sn_proposal_workspace_bytes(int B, int A, int Fh, int Fw, int pre_nms_top_n, int post_nms_top_n);

@@ -30,6 +30,7 @@ EXTRA = {
     "infer.hip": ["-ffp-contract=off"],
     "host_inference.cpp": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
+    "coco_eval.hip": ["-ffp-contract=off"],
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

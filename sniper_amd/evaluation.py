@@ -1,0 +1,297 @@
+"""COCO box evaluation on the device: the last line of the reference's test run, `imdb.evaluate_detections(all_boxes)`
+(lib/inference.py:523-527 -> lib/dataset/coco.py -> lib/dataset/pycocotools/cocoeval.py).
+
+    result = evaluate_detections(all_boxes, roidb, num_classes)      # all_boxes as Tester.aggregate returns it
+    print(result.summary())
+
+The per-image matching and the accumulation run as sn_coco_match / sn_coco_accumulate (sniper_amd/csrc/coco_eval.hip, DESIGN.md
+section 19): float64 IoU, integer counts, a few float64 divisions -- `precision` and `recall` are the reference's arrays on their
+bits.  The host's share is the conversion of the detections into the reference's result rows (coco.py:36-48 and COCO.loadRes),
+the CSR offsets of the (category, image) problems (numpy, vectorised) and the twelve means of summarize().  There is no CPU
+fallback: without the kernel library or a GPU, evaluate() raises.
+"""
+import numpy as np
+
+__all__ = ['Params', 'COCOBoxEvaluator', 'COCOBoxResult', 'evaluate_detections', 'round_half_even_decimal']
+
+
+class Params(object):
+    """The reference's Params (cocoeval.py:436-445).  useSegm and useCats = 0 are not implemented."""
+
+    def __init__(self):
+        self.iouThrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        self.recThrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+        self.maxDets = [1, 10, 100]
+        self.areaRng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+        self.useSegm = 0
+        self.useCats = 1
+
+
+def round_half_even_decimal(x, ndigits):
+    """Python's round(float(v), ndigits) for every v of a float64 array (the reference rounds with the builtin: correctly rounded in
+    decimal, which np.round -- rint(v * 10**n) / 10**n -- misses where v * 10**n lands on the other side of a half).  Vectorised:
+    rint(v * 10**n) / 10**n is the builtin's answer whenever v * 10**n is not within 1e-6 of a half (the quotient k / 10**n is the
+    double nearest to that decimal either way); the few values that are go through the builtin."""
+    x = np.asarray(x, np.float64)
+    s = float(10 ** ndigits)
+    y = x * s
+    out = np.rint(y) / s
+    near = np.abs(np.abs(y - np.floor(y)) - 0.5) < 1e-6
+    near |= ~(np.abs(y) < 2.0 ** 51)              # huge, inf, nan: leave them to the builtin too
+    if near.any():
+        flat, idx = out.reshape(-1), np.flatnonzero(near.reshape(-1))
+        src = x.reshape(-1)
+        flat[idx] = [round(float(src[i]), ndigits) for i in idx]
+        out = flat.reshape(x.shape)
+    return out
+
+
+_STAT_ROWS = ((1, None, 'all', 100), (1, .5, 'all', 100), (1, .75, 'all', 100), (1, None, 'small', 100), (1, None, 'medium', 100),
+              (1, None, 'large', 100), (0, None, 'all', 1), (0, None, 'all', 10), (0, None, 'all', 100), (0, None, 'small', 100),
+              (0, None, 'medium', 100), (0, None, 'large', 100))
+
+
+class COCOBoxResult(object):
+    """precision (T,R,K,A,M), recall (T,K,A,M), stats (12,), per_class_ap (K,), summary()"""
+
+    def __init__(self, precision, recall, params, cat_ids, timing=None):
+        self.precision, self.recall, self.params, self.cat_ids = precision, recall, params, list(cat_ids)
+        self.timing = timing or {}
+        self.stats, self._lines = self._summarize()
+        self.per_class_ap, self.mean_ap = self._per_class()
+
+    def _summarize(self):
+        """cocoeval.py:376-427: like the reference it addresses the default area ranges and maxDets by position"""
+        p = self.params
+        stats, lines = np.zeros((12,)), []
+        for n, (ap, iou_thr, area, max_dets) in enumerate(_STAT_ROWS):
+            aind = [i for i, name in enumerate(['all', 'small', 'medium', 'large']) if name == area]
+            mind = [i for i, md in enumerate([1, 10, 100]) if md == max_dets]
+            if aind[0] >= self.recall.shape[2] or mind[0] >= self.recall.shape[3]:
+                mean_s = -1                           # custom params with fewer ranges: the row does not exist
+            else:
+                if ap == 1:
+                    s = self.precision
+                    if iou_thr is not None:
+                        s = s[np.where(iou_thr == p.iouThrs)[0]]
+                    s = s[:, :, :, aind, mind]
+                else:
+                    s = self.recall[:, :, aind, mind]
+                mean_s = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+            stats[n] = mean_s
+            lines.append(' {:<18} {} @[ IoU={:<9} | area={:>6} | maxDets={:>3} ] = {}'.format(
+                'Average Precision' if ap == 1 else 'Average Recall', '(AP)' if ap == 1 else '(AR)',
+                '%0.2f:%0.2f' % (p.iouThrs[0], p.iouThrs[-1]) if iou_thr is None else '%0.2f' % iou_thr, area, '%d' % max_dets,
+                '%.3f' % float(mean_s)))
+        return stats, lines
+
+    def _per_class(self):
+        """coco.py:338-370: AP over IoU 0.50:0.95, area range 0, the last maxDets, per category (nan where a category has no entry
+        above -1, as np.mean of nothing is)"""
+        p = self.params
+
+        def thr_ind(thr):
+            hit = np.where((p.iouThrs > thr - 1e-5) & (p.iouThrs < thr + 1e-5))[0]
+            return int(hit[0]) if len(hit) else None
+        lo, hi = thr_ind(0.5), thr_ind(0.95)
+        K = self.precision.shape[2]
+        if lo is None or hi is None:
+            return np.full((K,), np.nan), float('nan')
+        pr = self.precision[lo:hi + 1, :, :, 0, self.precision.shape[4] - 1]
+        mean_of = lambda v: float(np.mean(v[v > -1])) if (v > -1).any() else float('nan')
+        return np.array([mean_of(pr[:, :, k]) for k in range(K)]), mean_of(pr)
+
+    def summary(self):
+        """the twelve lines of COCOeval.summarize()"""
+        return '\n'.join(self._lines)
+
+
+def _offsets(counts):
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=off[1:])
+    assert off[-1] < 2 ** 31
+    return off.astype(np.int32)
+
+
+class COCOBoxEvaluator(object):
+    """gt: dict of arrays over the NG ground-truth boxes in annotation order -- image (index into image_ids), category (index into
+    cat_ids), bbox (NG,4) xywh, area, iscrowd, ignore (optional, 0).  params: a Params (default: the reference's)."""
+
+    def __init__(self, gt, image_ids, cat_ids, params=None):
+        self.params = params or Params()
+        if getattr(self.params, 'useSegm', 0):
+            raise NotImplementedError('COCOBoxEvaluator: useSegm (mask evaluation) is not implemented, boxes only')
+        if not getattr(self.params, 'useCats', 1):
+            raise NotImplementedError('COCOBoxEvaluator: useCats = 0 (category-agnostic evaluation) is not implemented')
+        self.image_ids, self.cat_ids = list(image_ids), list(cat_ids)
+        n = len(gt['image'])
+        self.gt = {
+            'image': np.asarray(gt['image'], np.int64).reshape(n), 'category': np.asarray(gt['category'], np.int64).reshape(n),
+            'bbox': np.asarray(gt['bbox'], np.float64).reshape(n, 4), 'area': np.asarray(gt['area'], np.float64).reshape(n),
+            'iscrowd': np.asarray(gt['iscrowd']).reshape(n).astype(np.int64) != 0,
+            'ignore': (np.asarray(gt['ignore']).reshape(n).astype(np.int64) != 0) if 'ignore' in gt else np.zeros(n, bool),
+        }
+        I, K = len(self.image_ids), len(self.cat_ids)
+        assert n == 0 or (0 <= self.gt['image'].min() and self.gt['image'].max() < I), 'gt image index out of range'
+        assert n == 0 or (0 <= self.gt['category'].min() and self.gt['category'].max() < K), 'gt category index out of range'
+
+    @classmethod
+    def from_roidb(cls, roidb, num_classes, params=None):
+        """Ground truth = the roidb rows with gt_classes > 0; xywh = x1, y1, x2-x1+1, y2-y1+1 (float64); area = roidb['gt_areas']
+        where present, else w*h; iscrowd = roidb['gt_iscrowd'] where present, else 0.  Image ids are 1.., category ids 1..num_classes-1
+        (class c is category index c-1), annotation ids follow the roidb order."""
+        img, cat, box, area, crowd = [], [], [], [], []
+        for i, r in enumerate(roidb):
+            classes = np.asarray(r['gt_classes'])
+            keep = np.flatnonzero(classes > 0)
+            b = np.asarray(r['boxes'], np.float64)[keep].reshape(-1, 4)
+            xywh = np.stack((b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1), axis=1)
+            img.append(np.full(len(keep), i, np.int64))
+            cat.append(classes[keep].astype(np.int64) - 1)
+            box.append(xywh)
+            area.append(np.asarray(r['gt_areas'], np.float64)[keep] if 'gt_areas' in r else xywh[:, 2] * xywh[:, 3])
+            crowd.append(np.asarray(r['gt_iscrowd'])[keep].astype(np.int64) if 'gt_iscrowd' in r else np.zeros(len(keep), np.int64))
+        cat0 = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)
+        gt = {'image': cat0(img, (0,), np.int64), 'category': cat0(cat, (0,), np.int64), 'bbox': cat0(box, (0, 4), np.float64),
+              'area': cat0(area, (0,), np.float64), 'iscrowd': cat0(crowd, (0,), np.int64)}
+        return cls(gt, range(1, len(roidb) + 1), range(1, num_classes), params)
+
+    # ---- detections -----------------------------------------------------------------------------
+    def _counts(self, all_boxes):
+        K, I = len(self.cat_ids), len(self.image_ids)
+        assert len(all_boxes) == K + 1, 'all_boxes[class][image]: %d classes (with the background) for %d categories' % (len(all_boxes), K)
+        counts = np.zeros((K, I), np.int64)
+        for k in range(K):
+            assert len(all_boxes[k + 1]) == I, 'all_boxes[%d] has %d images, the ground truth %d' % (k + 1, len(all_boxes[k + 1]), I)
+            counts[k] = np.fromiter(map(len, all_boxes[k + 1]), np.int64, I)
+        return counts
+
+    def convert_detections(self, all_boxes):
+        """coco.py:36-48 + COCO.loadRes (pycocotools/coco.py:305-314) -> (dt rows (ND,6) float64 = x, y, w, h, score, area in
+        class-major, image, row order -- the order of the reference's result list, hence of its annotation ids -- and the (K, I)
+        row counts): float64 x2-x1+1, box values rounded to 1 decimal and the score to 8 like the builtin round does, area =
+        rounded w * rounded h."""
+        counts = self._counts(all_boxes)
+        cells = [d for per_image in all_boxes[1:] for d in per_image if len(d)]
+        rows = np.concatenate(cells, axis=0).astype(np.float64).reshape(-1, 5) if cells else np.zeros((0, 5), np.float64)
+        dt = np.empty((len(rows), 6), np.float64)
+        dt[:, 0], dt[:, 1] = rows[:, 0], rows[:, 1]
+        dt[:, 2] = rows[:, 2] - rows[:, 0] + 1
+        dt[:, 3] = rows[:, 3] - rows[:, 1] + 1
+        dt[:, :4] = round_half_even_decimal(dt[:, :4], 1)
+        dt[:, 4] = round_half_even_decimal(rows[:, 4], 8)
+        dt[:, 5] = dt[:, 2] * dt[:, 3]
+        return dt, counts
+
+    def _device_rows(self, all_boxes):
+        """round_results=False: the cells' rows stacked on the device (torch.cat of device cells = copies in HBM; host cells are stacked
+        and uploaded once) -> ((ND,5) device tensor float32 or float64, (K, I) counts)"""
+        import torch
+        from . import hip
+        counts = self._counts(all_boxes)
+        cells = [d for per_image in all_boxes[1:] for d in per_image if len(d)]
+        if not cells:
+            return torch.zeros((0, 5), dtype=torch.float64, device=hip.require_gpu()), counts
+        if all(isinstance(d, torch.Tensor) and d.is_cuda for d in cells):
+            assert len(set(d.dtype for d in cells)) == 1 and cells[0].dtype in (torch.float32, torch.float64)
+            return torch.cat([d.reshape(-1, 5) for d in cells]).contiguous(), counts
+        host = [d.cpu().numpy() if isinstance(d, torch.Tensor) else np.asarray(d) for d in cells]
+        dtype = np.float32 if all(h.dtype == np.float32 for h in host) else np.float64
+        return hip.dev(np.concatenate([h.reshape(-1, 5).astype(dtype, copy=False) for h in host])), counts
+
+    # ---- the problems ---------------------------------------------------------------------------
+    def _problems(self, dt_counts, max_det):
+        """CSR offsets of the (category, image) pairs that have a detection or a box, category-major then by image"""
+        K, I = dt_counts.shape
+        gkey = self.gt['category'] * I + self.gt['image']
+        gt_counts = np.bincount(gkey, minlength=K * I).reshape(K, I)
+        has = ((dt_counts + gt_counts) > 0).reshape(-1)
+        dc, gc = dt_counts.reshape(-1)[has], gt_counts.reshape(-1)[has]
+        prob_cat = np.flatnonzero(has) // I
+        return {
+            'P': int(has.sum()), 'dt_off': _offsets(dc), 'gt_off': _offsets(gc), 'kp_off': _offsets(np.minimum(dc, max_det)),
+            'cat_off': np.searchsorted(prob_cat, np.arange(K + 1)).astype(np.int32),
+            'gt_order': np.argsort(gkey, kind='stable'),          # boxes grouped by problem, annotation order inside
+            'max_dt': int(dc.max()) if len(dc) else 0, 'max_gt': int(gc.max()) if len(gc) else 0,
+        }
+
+    def evaluate(self, all_boxes, round_results=True, return_matches=False):
+        """all_boxes[class][image] = (n,5) rows x1, y1, x2, y2, score (class 0 = background) -> COCOBoxResult.
+        round_results=False skips the reference's rounding of the result rows (1 decimal for boxes, 8 for scores) and takes device-
+        resident rows (CUDA tensors in the cells) without a host copy: the numbers are then those of the unrounded detections, NOT the
+        reference's.  return_matches adds the per-image arrays (sn_coco_match's outputs and the offsets) as result.matches."""
+        import torch
+        from . import hip
+        p = self.params
+        dev = hip.require_gpu()
+        iou_thrs, rec_thrs = np.asarray(p.iouThrs, np.float64), np.asarray(p.recThrs, np.float64)
+        area_rng = np.asarray(p.areaRng, np.float64).reshape(-1, 2)
+        max_dets = np.asarray(sorted(p.maxDets), np.int32)
+        T, R, A, M, K = len(iou_thrs), len(rec_thrs), len(area_rng), len(max_dets), len(self.cat_ids)
+        max_det = int(max_dets[-1])
+        t0 = _now(torch)
+        rows = None
+        if round_results:
+            dt_host, counts = self.convert_detections(all_boxes)
+            ND = len(dt_host)
+        else:
+            rows, counts = self._device_rows(all_boxes)
+            ND = len(rows)
+        pr = self._problems(counts, max_det)
+        P, NG = pr['P'], len(self.gt['image'])
+        if P == 0:                                    # nothing to evaluate: every category is absent
+            return COCOBoxResult(-np.ones((T, R, K, A, M)), -np.ones((T, K, A, M)), p, self.cat_ids)
+        NK = int(pr['kp_off'][-1])
+        o = pr['gt_order']
+        gt_rows = np.concatenate((self.gt['bbox'][o], self.gt['area'][o, None]), axis=1) if NG else np.zeros((1, 5))
+        flags = (self.gt['iscrowd'][o].astype(np.uint8) | (self.gt['ignore'][o].astype(np.uint8) << 1)) if NG else np.zeros(1, np.uint8)
+        kept_per_cat = np.diff(pr['kp_off'][pr['cat_off']].astype(np.int64))
+        t1 = _now(torch)
+        if rows is None:
+            d_dt = hip.dev(dt_host) if ND else torch.zeros((1, 6), dtype=torch.float64, device=dev)
+        else:
+            d_dt = torch.empty((max(ND, 1), 6), dtype=torch.float64, device=dev)
+            if ND:
+                hip.call('sn_coco_pack_rows', rows, int(rows.dtype == torch.float32), None, ND, d_dt, hip.stream())
+        d_gt, d_flags = hip.dev(gt_rows), hip.dev(flags)
+        d_dt_off, d_gt_off, d_kp_off, d_cat_off = (hip.dev(pr[k]) for k in ('dt_off', 'gt_off', 'kp_off', 'cat_off'))
+        d_iou, d_rec, d_area = hip.dev(iou_thrs), hip.dev(rec_thrs), hip.dev(area_rng)
+        i32 = lambda *shape: torch.empty([max(int(np.prod(shape)), 1)], dtype=torch.int32, device=dev)
+        u8 = lambda *shape: torch.empty([max(int(np.prod(shape)), 1)], dtype=torch.uint8, device=dev)
+        dt_rank, dt_match, dt_ignore = i32(NK), i32(A, T, NK), u8(A, T, NK)
+        gt_match, gt_ignore = i32(A, T, NG), u8(A, NG)
+        precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+        recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(hip.query('sn_coco_accumulate_workspace_bytes', NK, T, A)), dtype=torch.uint8, device=dev)
+        t2 = _now(torch)
+        hip.call('sn_coco_match', d_dt, d_dt_off, d_kp_off, d_gt, d_flags, d_gt_off, d_iou, d_area, P, T, A, max_det, pr['max_dt'],
+                 pr['max_gt'], NK, NG, dt_rank, dt_match, dt_ignore, gt_match, gt_ignore, hip.stream())
+        tm = _now(torch)
+        hip.call('sn_coco_accumulate', d_dt, d_dt_off, d_kp_off, d_gt_off, d_cat_off, dt_rank, dt_match, dt_ignore, gt_ignore, d_rec,
+                 max_dets, P, K, T, A, M, R, max_det, int(kept_per_cat.max()), NK, NG, ws, ws.numel(), precision, recall, hip.stream())
+        t3 = _now(torch)
+        h_precision, h_recall = precision.cpu().numpy(), recall.cpu().numpy()
+        t4 = _now(torch)
+        # seconds: host = result rows + CSR offsets, upload = allocations + copies to the device, kernels = sn_coco_match +
+        # sn_coco_accumulate, download = precision + recall to the host
+        res = COCOBoxResult(h_precision, h_recall, p, self.cat_ids,
+                            {'host_s': t1 - t0, 'upload_s': t2 - t1, 'kernels_s': t3 - t2, 'match_s': tm - t2, 'accumulate_s': t3 - tm, 'download_s': t4 - t3, 'problems': P,
+                             'detections': ND, 'kept': NK, 'boxes': NG})
+        if return_matches:
+            res.matches = dict(pr, NK=NK, dt_rank=dt_rank[:NK].cpu().numpy(), dt_match=dt_match[:A * T * NK].reshape(A, T, NK).cpu().numpy(),
+                               dt_ignore=dt_ignore[:A * T * NK].reshape(A, T, NK).cpu().numpy(),
+                               gt_match=gt_match[:A * T * NG].reshape(A, T, NG).cpu().numpy(),
+                               gt_ignore=gt_ignore[:A * NG].reshape(A, NG).cpu().numpy(), dt=d_dt[:ND].cpu().numpy())
+        return res
+
+
+def _now(torch):
+    import time
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def evaluate_detections(all_boxes, roidb, num_classes, params=None, round_results=True):
+    """`imdb.evaluate_detections(all_boxes)` of the reference's test run in one call: ground truth from the roidb, detections as
+    Tester.aggregate / imdb_detection_wrapper return them -> COCOBoxResult"""
+    return COCOBoxEvaluator.from_roidb(roidb, num_classes, params).evaluate(all_boxes, round_results=round_results)
