@@ -511,6 +511,61 @@ int sn_coco_accumulate(const double *dt, const int32_t *dt_off, const int32_t *k
                        int max_kept_per_category, long NK, long NG, void *ws, size_t ws_bytes, double *precision, double *recall,
                        sn_stream_t stream);
 
+/* PASCAL VOC box evaluation (lib/dataset/pascal_voc_eval.py:116-181 voc_eval, :39-70 voc_ap).  float64 and integer counts
+ * throughout: `rec`, `prec` and `ap07` are the reference's bits, `ap_area` is its sum in another order (each term >= 0, every partial
+ * sum <= 1: within (n - 1) * 2^-53 of the exact sum for n recall changes).  A PROBLEM is one (class, image) pair with at least one
+ * detection or one box; the P problems are stored class-major, then by image.  All tensors are device pointers except h_ap07_thrs.
+ *   dt_box    (ND,4) f64   x1, y1, x2, y2 as the result file holds them (1-based), a problem's detections contiguous in arrival
+ *                          order;  dt_score (ND) f64;  dt_off (P+1) i32
+ *   gt_box    (NG,4) f64   x1, y1, x2, y2 as the annotation holds them;  gt_difficult (NG) u8;  gt_off (P+1) i32
+ *   cat_off   (K+1) i32    the first problem of every class (cat_off[k] == cat_off[k+1]: the class has neither detections nor boxes)
+ *   iou_thrs  (T) f64;  h_ap07_thrs (11) f64 in HOST memory: the values of np.arange(0., 1.1, 0.1).
+ * PRECONDITIONS, not checked on the device: every row is finite with x2 >= x1 and y2 >= y1 (so that no union is 0), scores are
+ * finite.
+ * sn_voc_match, one launch, per problem.  IoU = iw * ih / ((area_d + area_g) - iw * ih) with iw = max(min(x2) - max(x1) + 1, 0) and
+ * areas (x2 - x1 + 1) * (y2 - y1 + 1).  Per detection: ovmax and the FIRST box of maximal IoU (on equal IoU the EARLIER box,
+ * np.argmax; the opposite of sn_coco_match); a problem without boxes gives ovmax = -inf.  The detections of a problem are ranked by
+ * descending score, EQUAL SCORES BY ARRIVAL ORDER (the reference's np.argsort(-confidence) is not stable and leaves their order
+ * undefined; this library defines it).  For every threshold t: ovmax > t (strict) and the box is difficult: neither tp nor fp;
+ * ovmax > t, the box is not difficult and the detection is the first in rank among those claiming that box: tp, later claimants fp;
+ * ovmax <= t: fp.  A detection never falls back to a second-best box.
+ *   dt_best   (ND) i32      1 + arrival index (within the problem) of the argmax box, 0 = none
+ *   dt_iou    (ND) f64      ovmax
+ *   dt_tp, dt_fp (T,ND) u8
+ *   gt_det    (T,NG) i32    1 + arrival index (within the problem) of the detection that took the box, 0 = none (always 0 for a
+ *                           difficult box)
+ * sn_voc_accumulate, two launches.  The detections of a class are ordered by (descending score, position in the concatenation of
+ * the class's problems) -- what a stable sort of -score yields.  Per (t, class): inclusive integer scans of tp and fp,
+ * rec = tp / (double)npos, prec = tp / max(tp + fp, 2^-52); ap07 = eleven sequential `ap += p / 11.` with p = the max of prec where
+ * rec >= h_ap07_thrs[j], else 0; ap_area = the sum of (mrec[i+1] - mrec[i]) * mpre[i+1] over the recall changes, with the sentinels
+ * and the reverse running max of voc_ap.  A class with detections and npos = 0 has rec = nan, ap07 = 0 and ap_area = nan, as the
+ * reference; a class without detections has both APs 0.
+ *   order     (ND) i32      order[c0 + r] = position in the detection list of the class's r-th detection (c0 = the class's first row)
+ *   rec, prec (T,ND) f64    the curves, in sorted order
+ *   npos      (K) i32       non-difficult boxes per class
+ *   ap07, ap_area (T,K) f64
+ * Every element of every output is written on every call.  max_dt_per_problem, max_gt_per_problem, max_dt_per_class: the largest
+ * D_p, G_p and per-class detection count, which the caller knows from building the offsets; the first two are checked against the
+ * limits, the last sizes the ordering launch.
+ * Refused before any launch, by a message that names the function and the condition: a NULL tensor; P < 1; T below 1 or above
+ * SN_VOC_MAX_T; K above 65535; a problem with more than SN_VOC_MAX_DT detections or SN_VOC_MAX_GT boxes (both live in LDS); row
+ * counts past 32-bit indexing; a workspace shorter than sn_voc_accumulate_workspace_bytes(ND, T) (0 for a refused shape).
+ * sn_voc_limits: h_out5 (HOST) = {MAX_DT, MAX_GT, MAX_T, detections per workgroup of the ordering launch, detections per chunk of
+ * the scans}.  No float atomics (one integer min in LDS), no host read-back, the same bits every run. */
+#define SN_VOC_MAX_DT 1024
+#define SN_VOC_MAX_GT 256
+#define SN_VOC_MAX_T 8
+int sn_voc_limits(int32_t *h_out5);
+int sn_voc_match(const double *dt_box, const double *dt_score, const int32_t *dt_off, const double *gt_box,
+                 const uint8_t *gt_difficult, const int32_t *gt_off, const double *iou_thrs, int P, int T, int max_dt_per_problem,
+                 int max_gt_per_problem, long ND, long NG, int32_t *dt_best, double *dt_iou, uint8_t *dt_tp, uint8_t *dt_fp,
+                 int32_t *gt_det, sn_stream_t stream);
+size_t sn_voc_accumulate_workspace_bytes(long ND, int T);
+int sn_voc_accumulate(const double *dt_score, const int32_t *dt_off, const int32_t *gt_off, const int32_t *cat_off,
+                      const uint8_t *gt_difficult, const uint8_t *dt_tp, const uint8_t *dt_fp, const double *h_ap07_thrs, int P, int K,
+                      int T, int max_dt_per_class, long ND, long NG, void *ws, size_t ws_bytes, int32_t *order, double *rec,
+                      double *prec, int32_t *npos, double *ap07, double *ap_area, sn_stream_t stream);
+
 /* MultiProposal (:347-355) / MultiProposalTarget (:283-284).  cls_prob (B,2,A*Fh,Fw), bbox_pred (B,4A,Fh,Fw),
  * im_info (B,3), gt_boxes (B,G,5), valid_ranges (B,2), base_anchors (A,4): all fp32 device. */
 size_t sn_proposal_workspace_bytes(int B, int A, int Fh, int Fw, int pre_nms_top_n, int post_nms_top_n);

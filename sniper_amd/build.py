@@ -31,6 +31,7 @@ EXTRA = {
     "host_inference.cpp": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
+    "voc_eval.hip": ["-ffp-contract=off"],
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

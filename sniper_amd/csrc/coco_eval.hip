@@ -27,6 +27,7 @@
 // every run.  The file is compiled with -ffp-contract=off (sniper_amd/build.py) and says so itself below: the reference is built
 // for baseline x86-64 and rounds da+ga-w*h twice.
 #include "common.h"
+#include "eval_order.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +39,7 @@ constexpr int kMaxDt = SN_COCO_MAX_DT;     // detections of one problem: their s
 constexpr int kMaxGt = SN_COCO_MAX_GT;     // boxes of one problem: four per lane, in registers
 constexpr int kGtPerLane = kMaxGt / kWave;
 constexpr int kMaxT = 16, kMaxA = 8, kMaxM = 4, kMaxR = 128;
-constexpr int kSortTile = 256, kScanChunk = 256;
+constexpr int kSortTile = kEvalSortTile, kScanChunk = kEvalScanChunk;     // eval_order.h: shared with voc_eval.hip
 constexpr double kEps = 2.220446049250313e-16;   // np.spacing(1)
 
 static_assert(kGtPerLane * kWave == kMaxGt, "a lane holds a whole number of boxes");
@@ -249,49 +250,18 @@ __global__ __launch_bounds__(256) void coco_keys_kernel(const double *__restrict
   }
 }
 
-// grid (tiles, K): the order of category k's kept detections by (descending score, position)
+// grid (tiles, K): the order of category k's kept detections by (descending score, position) -- eval_order.h
 __global__ __launch_bounds__(kSortTile) void coco_order_kernel(const int32_t *__restrict__ cat_off, const int32_t *__restrict__ kp_off,
                                                                const double *__restrict__ ws_score, int32_t *__restrict__ ws_order) {
   __shared__ double s_tile[kSortTile];
-  const int k = blockIdx.y, tid = threadIdx.x;
+  const int k = blockIdx.y;
   const int c0 = kp_off[cat_off[k]], N = kp_off[cat_off[k + 1]] - c0;
-  const int i = blockIdx.x * kSortTile + tid;
-  if (blockIdx.x * kSortTile >= N) return;       // the whole workgroup leaves: no barrier is skipped by a part of it
-  const double si = i < N ? ws_score[c0 + i] : 0.;
-  int before = 0;
-  for (int base = 0; base < N; base += kSortTile) {
-    __syncthreads();
-    if (base + tid < N) s_tile[tid] = ws_score[c0 + base + tid];
-    __syncthreads();
-    const int n = N - base < kSortTile ? N - base : kSortTile;
-    for (int j = 0; j < n; ++j) {
-      const double sj = s_tile[j];
-      before += (sj > si) | ((sj == si) & (base + j < i));
-    }
-  }
-  if (i < N) ws_order[c0 + before] = i;
+  sn_eval_order_tile(c0, N, ws_score, ws_order, 0, s_tile);
 }
 
 struct MaxDets {
   int n, v[kMaxM];
 };
-
-__device__ __forceinline__ int wave_scan_add(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int o = __shfl_up(v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ double wave_scan_max_rev(double v, int lane) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double o = __shfl_down(v, off, 64);
-    if (lane + off < kWave) v = fmax(v, o);
-  }
-  return v;
-}
 
 // grid (A*T, K): precision[t, :, k, a, :] and recall[t, k, a, :]
 __global__ __launch_bounds__(kScanChunk) void coco_curves_kernel(

@@ -9,6 +9,10 @@ section 19): float64 IoU, integer counts, a few float64 divisions -- `precision`
 bits.  The host's share is the conversion of the detections into the reference's result rows (coco.py:36-48 and COCO.loadRes),
 the CSR offsets of the (category, image) problems (numpy, vectorised) and the twelve means of summarize().  There is no CPU
 fallback: without the kernel library or a GPU, evaluate() raises.
+
+The reference's second data set, PASCAL VOC, ends in the same line through voc_eval / voc_ap: evaluate_detections_voc and
+VOCBoxEvaluator in the second half of this file (sn_voc_match / sn_voc_accumulate, sniper_amd/csrc/voc_eval.hip, DESIGN.md
+section 20).
 """
 import numpy as np
 
@@ -113,6 +117,32 @@ def _offsets(counts):
     return off.astype(np.int32)
 
 
+def _cell_counts(all_boxes, K, I):
+    """(K, I) row counts of all_boxes[class][image] (class 0 = background), its shape checked (both evaluators)"""
+    assert len(all_boxes) == K + 1, 'all_boxes[class][image]: %d classes (with the background) for %d categories' % (len(all_boxes), K)
+    counts = np.zeros((K, I), np.int64)
+    for k in range(K):
+        assert len(all_boxes[k + 1]) == I, 'all_boxes[%d] has %d images, the ground truth %d' % (k + 1, len(all_boxes[k + 1]), I)
+        counts[k] = np.fromiter(map(len, all_boxes[k + 1]), np.int64, I)
+    return counts
+
+
+def _problem_offsets(dt_counts, gt_category, gt_image):
+    """CSR offsets of the (category, image) pairs that have a detection or a box, category-major then by image (both evaluators)"""
+    K, I = dt_counts.shape
+    gkey = gt_category * I + gt_image
+    gt_counts = np.bincount(gkey, minlength=K * I).reshape(K, I)
+    has = ((dt_counts + gt_counts) > 0).reshape(-1)
+    dc, gc = dt_counts.reshape(-1)[has], gt_counts.reshape(-1)[has]
+    prob_cat = np.flatnonzero(has) // I
+    return {
+        'P': int(has.sum()), 'dt_off': _offsets(dc), 'gt_off': _offsets(gc), 'dt_counts': dc,
+        'cat_off': np.searchsorted(prob_cat, np.arange(K + 1)).astype(np.int32),
+        'gt_order': np.argsort(gkey, kind='stable'),          # boxes grouped by problem, annotation order inside
+        'max_dt': int(dc.max()) if len(dc) else 0, 'max_gt': int(gc.max()) if len(gc) else 0,
+    }
+
+
 class COCOBoxEvaluator(object):
     """gt: dict of arrays over the NG ground-truth boxes in annotation order -- image (index into image_ids), category (index into
     cat_ids), bbox (NG,4) xywh, area, iscrowd, ignore (optional, 0).  params: a Params (default: the reference's)."""
@@ -158,13 +188,7 @@ class COCOBoxEvaluator(object):
 
     # ---- detections -----------------------------------------------------------------------------
     def _counts(self, all_boxes):
-        K, I = len(self.cat_ids), len(self.image_ids)
-        assert len(all_boxes) == K + 1, 'all_boxes[class][image]: %d classes (with the background) for %d categories' % (len(all_boxes), K)
-        counts = np.zeros((K, I), np.int64)
-        for k in range(K):
-            assert len(all_boxes[k + 1]) == I, 'all_boxes[%d] has %d images, the ground truth %d' % (k + 1, len(all_boxes[k + 1]), I)
-            counts[k] = np.fromiter(map(len, all_boxes[k + 1]), np.int64, I)
-        return counts
+        return _cell_counts(all_boxes, len(self.cat_ids), len(self.image_ids))
 
     def convert_detections(self, all_boxes):
         """coco.py:36-48 + COCO.loadRes (pycocotools/coco.py:305-314) -> (dt rows (ND,6) float64 = x, y, w, h, score, area in
@@ -202,18 +226,9 @@ class COCOBoxEvaluator(object):
     # ---- the problems ---------------------------------------------------------------------------
     def _problems(self, dt_counts, max_det):
         """CSR offsets of the (category, image) pairs that have a detection or a box, category-major then by image"""
-        K, I = dt_counts.shape
-        gkey = self.gt['category'] * I + self.gt['image']
-        gt_counts = np.bincount(gkey, minlength=K * I).reshape(K, I)
-        has = ((dt_counts + gt_counts) > 0).reshape(-1)
-        dc, gc = dt_counts.reshape(-1)[has], gt_counts.reshape(-1)[has]
-        prob_cat = np.flatnonzero(has) // I
-        return {
-            'P': int(has.sum()), 'dt_off': _offsets(dc), 'gt_off': _offsets(gc), 'kp_off': _offsets(np.minimum(dc, max_det)),
-            'cat_off': np.searchsorted(prob_cat, np.arange(K + 1)).astype(np.int32),
-            'gt_order': np.argsort(gkey, kind='stable'),          # boxes grouped by problem, annotation order inside
-            'max_dt': int(dc.max()) if len(dc) else 0, 'max_gt': int(gc.max()) if len(gc) else 0,
-        }
+        pr = _problem_offsets(dt_counts, self.gt['category'], self.gt['image'])
+        pr['kp_off'] = _offsets(np.minimum(pr.pop('dt_counts'), max_det))
+        return pr
 
     def evaluate(self, all_boxes, round_results=True, return_matches=False):
         """all_boxes[class][image] = (n,5) rows x1, y1, x2, y2, score (class 0 = background) -> COCOBoxResult.
@@ -295,3 +310,181 @@ def evaluate_detections(all_boxes, roidb, num_classes, params=None, round_result
     """`imdb.evaluate_detections(all_boxes)` of the reference's test run in one call: ground truth from the roidb, detections as
     Tester.aggregate / imdb_detection_wrapper return them -> COCOBoxResult"""
     return COCOBoxEvaluator.from_roidb(roidb, num_classes, params).evaluate(all_boxes, round_results=round_results)
+
+
+# ---- PASCAL VOC --------------------------------------------------------------------------------------
+# The reference's second data set (configs/faster/sniper_res101_e2e_pascal_voc.yml) ends in the same line through
+# PascalVOC.evaluate_detections -> write_pascal_results -> do_python_eval -> voc_eval / voc_ap (lib/dataset/pascal_voc.py:246-265,
+# 395-456, lib/dataset/pascal_voc_eval.py:39-181).  sn_voc_match / sn_voc_accumulate (sniper_amd/csrc/voc_eval.hip, DESIGN.md
+# section 20) do the matching and the curves; the host converts the detections into the rows of the result files and takes the means.
+#
+# EQUAL SCORES.  Rounding scores to 3 decimals makes equal scores common, and the reference's np.argsort(-confidence) is not a
+# stable sort, so the reference itself does not define their order.  This project does: arrival order = class-major, image, row.
+VOC_CLASSES = ('aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable', 'dog', 'horse',
+               'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor')
+
+__all__ += ['VOCBoxEvaluator', 'VOCBoxResult', 'evaluate_detections_voc', 'VOC_CLASSES']
+
+
+class VOCBoxResult(object):
+    """ap07, ap_area (T,K); ap = the one `use_07_metric` chooses; mean_ap (T,); npos (K,); summary()"""
+
+    def __init__(self, ap07, ap_area, npos, class_names, use_07_metric, thresholds, timing=None):
+        self.ap07, self.ap_area, self.npos = ap07, ap_area, npos
+        self.class_names, self.use_07_metric, self.thresholds = list(class_names), bool(use_07_metric), tuple(thresholds)
+        self.ap = ap07 if use_07_metric else ap_area
+        self.mean_ap = np.array([np.mean(self.ap[t]) for t in range(len(self.thresholds))], np.float64)
+        self.timing = timing or {}
+
+    def summary(self):
+        """the info_str of do_python_eval (pascal_voc.py:417-456), character for character"""
+        blocks = []
+        for t, thr in enumerate(self.thresholds):
+            lines = ['AP for {} = {:.4f}'.format(c, self.ap[t, k]) for k, c in enumerate(self.class_names)]
+            lines.append('Mean AP@{:g} = {:.4f}'.format(thr, self.mean_ap[t]))
+            blocks.append('\n'.join(lines))
+        return 'VOC07 metric? ' + ('Y' if self.use_07_metric else 'No') + '\n' + '\n\n'.join(blocks)
+
+    def curve(self, t, k):
+        """(rec, prec) of class k at threshold t (evaluate(..., return_curves=True) only)"""
+        lo, hi = self.curves['cls_off'][k], self.curves['cls_off'][k + 1]
+        return self.curves['rec'][t, lo:hi], self.curves['prec'][t, lo:hi]
+
+
+class VOCBoxEvaluator(object):
+    """gt: dict of arrays over the NG annotated boxes in annotation order -- image (index, 0 .. num_images - 1), category (index
+    into class_names), bbox (NG,4) x1, y1, x2, y2 AS THE ANNOTATION HOLDS THEM (1-based like the XML), difficult.  class_names: the K
+    foreground classes (a leading '__background__' is dropped).  use_07_metric: the 11-point AP (True) or the area under the
+    monotone envelope (False) as `ap`; both are computed on every call."""
+
+    def __init__(self, gt, num_images, class_names, use_07_metric, thresholds=(0.5, 0.7)):
+        names = list(class_names)
+        self.class_names = names[1:] if names and names[0] == '__background__' else names
+        self.num_images, self.use_07_metric = int(num_images), bool(use_07_metric)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        n = len(gt['image'])
+        self.gt = {
+            'image': np.asarray(gt['image'], np.int64).reshape(n), 'category': np.asarray(gt['category'], np.int64).reshape(n),
+            'bbox': np.asarray(gt['bbox'], np.float64).reshape(n, 4),
+            'difficult': (np.asarray(gt['difficult']).reshape(n).astype(np.int64) != 0) if 'difficult' in gt else np.zeros(n, bool),
+        }
+        K = len(self.class_names)
+        assert n == 0 or (0 <= self.gt['image'].min() and self.gt['image'].max() < self.num_images), 'gt image index out of range'
+        assert n == 0 or (0 <= self.gt['category'].min() and self.gt['category'].max() < K), 'gt category index out of range'
+
+    @classmethod
+    def from_roidb(cls, roidb, num_classes, class_names=None, year='2007'):
+        """Ground truth = the roidb rows with gt_classes > 0; boxes = roidb['boxes'] + 1 (the loader subtracted 1 from the XML's
+        pixel indices, pascal_voc.py:170-173); difficult = roidb[i]['gt_difficult'] where present, else all zero; use_07_metric by
+        the reference's rule, year == 'SDS' or int(year) < 2010.
+
+        NOTE: the reference's own roidb DROPS difficult objects (use_diff: False) while voc_eval reads them from the XML, where
+        they shield the detections that match them from counting as false positives.  A caller who wants the reference's numbers
+        on real VOC must keep those objects in the roidb and pass their flags as 'gt_difficult'."""
+        if class_names is None:
+            class_names = VOC_CLASSES if num_classes == len(VOC_CLASSES) + 1 else ['class%d' % c for c in range(1, num_classes)]
+        names = list(class_names)
+        names = names[1:] if names and names[0] == '__background__' else names
+        assert len(names) == num_classes - 1, '%d class names for %d classes with the background' % (len(names), num_classes)
+        img, cat, box, diff = [], [], [], []
+        for i, r in enumerate(roidb):
+            classes = np.asarray(r['gt_classes'])
+            keep = np.flatnonzero(classes > 0)
+            img.append(np.full(len(keep), i, np.int64))
+            cat.append(classes[keep].astype(np.int64) - 1)
+            box.append(np.asarray(r['boxes'], np.float64)[keep].reshape(-1, 4) + 1)
+            diff.append(np.asarray(r['gt_difficult'])[keep].astype(np.int64) if 'gt_difficult' in r else np.zeros(len(keep), np.int64))
+        cat0 = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)
+        gt = {'image': cat0(img, (0,), np.int64), 'category': cat0(cat, (0,), np.int64), 'bbox': cat0(box, (0, 4), np.float64),
+              'difficult': cat0(diff, (0,), np.int64)}
+        return cls(gt, len(roidb), names, year == 'SDS' or int(year) < 2010)
+
+    def convert_detections(self, all_boxes):
+        """The rows write_pascal_results writes ('{:.3f}' of the score, '{:.1f}' of v + 1, pascal_voc.py:412-415) and voc_eval reads
+        back -> ((ND,5) float64 rows x1, y1, x2, y2, score in class-major, image, row order, (K, I) row counts).  v + 1 is taken in
+        the rows' own dtype (float32 rows add in float32, as dets[k, 0] + 1 does), then converted to float64 and rounded like the
+        format does: correctly in decimal, halves to even."""
+        counts = _cell_counts(all_boxes, len(self.class_names), self.num_images)
+        cells = [d for per_image in all_boxes[1:] for d in per_image if len(d)]
+        cells = [np.asarray(d.cpu() if hasattr(d, 'cpu') else d).reshape(-1, 5) for d in cells]
+        if not cells:
+            return np.zeros((0, 5), np.float64), counts
+        if len(set(c.dtype for c in cells)) == 1:
+            raw = np.concatenate(cells, axis=0)
+            plus = (raw[:, :4] + 1).astype(np.float64)
+            score = raw[:, 4].astype(np.float64)
+        else:
+            plus = np.concatenate([(c[:, :4] + 1).astype(np.float64) for c in cells], axis=0)
+            score = np.concatenate([c[:, 4].astype(np.float64) for c in cells], axis=0)
+        rows = np.empty((len(plus), 5), np.float64)
+        rows[:, :4] = round_half_even_decimal(plus, 1)
+        rows[:, 4] = round_half_even_decimal(score, 3)
+        return rows, counts
+
+    def evaluate(self, all_boxes, return_curves=False):
+        """all_boxes[class][image] = (n,5) rows x1, y1, x2, y2, score, 0-based pixel indices as the test run holds them (class 0 =
+        background) -> VOCBoxResult.  return_curves adds result.curves: rec and prec (T,ND) in each class's sorted order, order,
+        cls_off (K+1) (class k's curve is [cls_off[k], cls_off[k+1]), result.curve(t, k)), the outputs of sn_voc_match (dt_best,
+        dt_iou, dt_tp, dt_fp, gt_det), the rows and the offsets."""
+        import torch
+        from . import hip
+        dev = hip.require_gpu()
+        thrs = np.asarray(self.thresholds, np.float64)
+        T, K = len(thrs), len(self.class_names)
+        t0 = _now(torch)
+        rows, counts = self.convert_detections(all_boxes)
+        ND, NG = len(rows), len(self.gt['image'])
+        pr = _problem_offsets(counts, self.gt['category'], self.gt['image'])
+        P = pr['P']
+        if P == 0:                                    # neither detections nor boxes: every AP is 0, as the reference's
+            return VOCBoxResult(np.zeros((T, K)), np.zeros((T, K)), np.zeros(K, np.int32), self.class_names, self.use_07_metric, self.thresholds)
+        o = pr['gt_order']
+        gt_rows = self.gt['bbox'][o] if NG else np.zeros((1, 4))
+        difficult = self.gt['difficult'][o].astype(np.uint8) if NG else np.zeros(1, np.uint8)
+        cls_off = pr['dt_off'][pr['cat_off']]
+        per_class = np.diff(cls_off.astype(np.int64))
+        ap07_thrs = np.arange(0., 1.1, 0.1)
+        assert ap07_thrs.shape == (11,) and ap07_thrs.dtype == np.float64
+        t1 = _now(torch)
+        d_box = hip.dev(np.ascontiguousarray(rows[:, :4])) if ND else torch.zeros((1, 4), dtype=torch.float64, device=dev)
+        d_score = hip.dev(np.ascontiguousarray(rows[:, 4])) if ND else torch.zeros((1,), dtype=torch.float64, device=dev)
+        d_gt, d_diff = hip.dev(gt_rows), hip.dev(difficult)
+        d_dt_off, d_gt_off, d_cat_off, d_thr = hip.dev(pr['dt_off']), hip.dev(pr['gt_off']), hip.dev(pr['cat_off']), hip.dev(thrs)
+        empty = lambda dtype, *shape: torch.empty([max(int(np.prod(shape)), 1)], dtype=dtype, device=dev)
+        dt_best, dt_iou = empty(torch.int32, ND), empty(torch.float64, ND)
+        dt_tp, dt_fp, gt_det = empty(torch.uint8, T, ND), empty(torch.uint8, T, ND), empty(torch.int32, T, NG)
+        order, rec, prec = empty(torch.int32, ND), empty(torch.float64, T, ND), empty(torch.float64, T, ND)
+        npos = torch.empty((K,), dtype=torch.int32, device=dev)
+        ap07 = torch.empty((T, K), dtype=torch.float64, device=dev)
+        ap_area = torch.empty((T, K), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(hip.query('sn_voc_accumulate_workspace_bytes', ND, T)), dtype=torch.uint8, device=dev)
+        t2 = _now(torch)
+        hip.call('sn_voc_match', d_box, d_score, d_dt_off, d_gt, d_diff, d_gt_off, d_thr, P, T, pr['max_dt'], pr['max_gt'], ND, NG,
+                 dt_best, dt_iou, dt_tp, dt_fp, gt_det, hip.stream())
+        tm = _now(torch)
+        hip.call('sn_voc_accumulate', d_score, d_dt_off, d_gt_off, d_cat_off, d_diff, dt_tp, dt_fp, ap07_thrs, P, K, T,
+                 int(per_class.max()), ND, NG, ws, ws.numel(), order, rec, prec, npos, ap07, ap_area, hip.stream())
+        t3 = _now(torch)
+        h_ap07, h_area, h_npos = ap07.cpu().numpy(), ap_area.cpu().numpy(), npos.cpu().numpy()
+        curves = None
+        if return_curves:
+            rd = lambda x, *shape: x[:int(np.prod(shape))].reshape(shape).cpu().numpy()
+            curves = dict(pr, cls_off=cls_off, rows=rows, rec=rd(rec, T, ND), prec=rd(prec, T, ND), order=rd(order, ND),
+                          dt_best=rd(dt_best, ND), dt_iou=rd(dt_iou, ND), dt_tp=rd(dt_tp, T, ND), dt_fp=rd(dt_fp, T, ND),
+                          gt_det=rd(gt_det, T, NG))
+        t4 = _now(torch)
+        # seconds, the keys of the COCO result: host = result rows + CSR offsets, upload = allocations + copies to the device,
+        # kernels = sn_voc_match + sn_voc_accumulate, download = the APs and npos (and the curves, if asked for) to the host
+        res = VOCBoxResult(h_ap07, h_area, h_npos, self.class_names, self.use_07_metric, self.thresholds,
+                           {'host_s': t1 - t0, 'upload_s': t2 - t1, 'kernels_s': t3 - t2, 'match_s': tm - t2, 'accumulate_s': t3 - tm,
+                            'download_s': t4 - t3, 'problems': P, 'detections': ND, 'kept': ND, 'boxes': NG})
+        if curves is not None:
+            res.curves = curves
+        return res
+
+
+def evaluate_detections_voc(all_boxes, roidb, num_classes, class_names=None, year='2007'):
+    """`imdb.evaluate_detections(all_boxes)` of the reference's PASCAL VOC test run in one call: ground truth from the roidb (see
+    VOCBoxEvaluator.from_roidb on difficult objects), detections as Tester.aggregate / imdb_detection_wrapper return them ->
+    VOCBoxResult; print(result.summary()) gives the reference's lines"""
+    return VOCBoxEvaluator.from_roidb(roidb, num_classes, class_names, year).evaluate(all_boxes)
