@@ -566,6 +566,52 @@ int sn_voc_accumulate(const double *dt_score, const int32_t *dt_off, const int32
                       int T, int max_dt_per_class, long ND, long NG, void *ws, size_t ws_bytes, int32_t *order, double *rec,
                       double *prec, int32_t *npos, double *ap07, double *ap_area, sn_stream_t stream);
 
+/* Proposal roidb (lib/dataset/imdb.py:81-204, 291-419): what turns an RPN proposals pickle into the roidb of the negative-chip run.
+ * Ragged batches of I images through (I+1) i32 prefix offsets; all tensors are device pointers except h_out6.  PRECONDITIONS, not
+ * checked on the device: rows are finite with x2 >= x1 and y2 >= y1 (so that no union is 0).
+ * sn_prop_nms -- nmsp, lib/nms/nms.py:48-86 (called from imdb.py:102-112 load_rpn_data).  rows (total,5) f32 x1, y1, x2, y2, score,
+ *   unsorted, image b's at [off[b], off[b+1]).  Per image: order by descending score, EQUAL SCORES THE LATER ROW FIRST (the
+ *   reference's argsort()[::-1] on an unstable sort leaves their order undefined; this is what a reversed stable argsort gives), walk
+ *   the order and suppress a row whose IoU with an earlier kept row is > thresh.  float32 throughout with the + 1 convention,
+ *   inter / (area_i + area_j - inter).  Three launches.
+ *     keep   (total) i32   at off[b]: the image's kept row indices (inside the image) in keep order, then -1
+ *     nkeep  (I) i32
+ *   max_n: the largest image.  ws: sn_prop_nms_workspace_bytes(total) (0 for a refused total).
+ * sn_prop_assign -- create_roidb_from_box_list, imdb.py:168-191.  boxes (total,4) f64, gt_box (NG,4) f64, gt_classes (NG) i32.
+ *   bbox_overlaps_cython (lib/bbox/bbox.pyx:35-56) in float64, iw * ih / ((bw * bh) + box_area - iw * ih), 0 when iw <= 0 or ih <= 0;
+ *   per box the row maximum and the FIRST index that attains it (np.argmax).  One launch.
+ *     max_ov  (total) f32  the maximum cast to float32 (0 in an image without ground truth)
+ *     max_cls (total) i32  gt_classes[argmax] when the maximum is > 0, else 0
+ *     argmax  (total) i32  index inside the image's ground truth, -1 in an image without
+ * sn_prop_recall -- the matching of evaluate_recall, imdb.py:329-374.  One problem = one (image, area range) pair.  gt_mask (NG) u8:
+ *   bit a set = the row belongs to range a (the host decides membership in the arrays' own dtype); thrs (T) f64.  Per problem with
+ *   N > 0 boxes and G_a rows of the range: min(N, G_a) rounds, each takes the largest remaining overlap among unused boxes and unused
+ *   rows, ties by LOWEST ROW then LOWEST BOX (the argmax(axis=0) / max(axis=0).argmax() pair), records it and retires both.  One
+ *   launch (and two memsets of the counters).
+ *     gt_ov   (A,NG) f64   at [a][gt_off[i] ..): the image's recorded values in round order, then zeros up to its G rows; the
+ *                          first G_a slots are the reference's _gt_overlaps (an image with N = 0 contributes none)
+ *     num_pos (A) i32      rows per range, images with N = 0 included
+ *     hits    (A,T) i32    the number of the G_a slots (the zeros of unplayed rounds included, as in the reference) >= thrs[t],
+ *                          over the images with N > 0; integer atomics: the same bytes every run
+ * max_g: the largest G of an image, refused above SN_PROP_MAX_GT (the boxes of an image live in LDS / registers); N has no cap.
+ * Refused before any launch, by a message that names the function and the condition: a NULL tensor; I < 1 (sn_prop_nms: I above
+ * 65535); A outside 1 .. 8; T outside 1 .. SN_PROP_MAX_T; max_g above the limit; max_n above total; row counts past 32-bit
+ * indexing; a short workspace.
+ * sn_prop_limits: h_out6 (HOST) = {MAX_GT, MAX_T, boxes per workgroup of the assign launch, threads (= columns per pass) of the
+ * recall workgroup, candidates per step of the NMS walk, rows per workgroup of the ordering launch}. */
+#define SN_PROP_MAX_GT 512
+#define SN_PROP_MAX_T 32
+int sn_prop_limits(int32_t *h_out6);
+size_t sn_prop_nms_workspace_bytes(long total);
+int sn_prop_nms(const float *rows, const int32_t *off, int I, int max_n, long total, float thresh, void *ws, size_t ws_bytes,
+                int32_t *keep, int32_t *nkeep, sn_stream_t stream);
+int sn_prop_assign(const double *boxes, const int32_t *box_off, const double *gt_box, const int32_t *gt_classes,
+                   const int32_t *gt_off, int I, int max_n, int max_g, long total, long NG, float *max_ov, int32_t *max_cls,
+                   int32_t *argmax, sn_stream_t stream);
+int sn_prop_recall(const double *boxes, const int32_t *box_off, const double *gt_box, const uint8_t *gt_mask, const int32_t *gt_off,
+                   const double *thrs, int I, int A, int T, int max_g, long total, long NG, double *gt_ov, int32_t *num_pos,
+                   int32_t *hits, sn_stream_t stream);
+
 /* MultiProposal (:347-355) / MultiProposalTarget (:283-284).  cls_prob (B,2,A*Fh,Fw), bbox_pred (B,4A,Fh,Fw),
  * im_info (B,3), gt_boxes (B,G,5), valid_ranges (B,2), base_anchors (A,4): all fp32 device. */
 size_t sn_proposal_workspace_bytes(int B, int A, int Fh, int Fw, int pre_nms_top_n, int post_nms_top_n);

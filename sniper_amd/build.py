@@ -32,6 +32,7 @@ EXTRA = {
     "mask.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
     "voc_eval.hip": ["-ffp-contract=off"],
+    "prop_roidb.hip": ["-ffp-contract=off"],
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

@@ -7,34 +7,13 @@
 // Reference algorithms: lib/bbox/bbox.pyx:17-95, lib/chips/cchips.cpp:14-177,
 // lib/data_utils/data_workers.py:133-371, lib/data_utils/generate_anchor.py.
 #include "common.h"
+#include "box_overlap.h"
 
 // ============================================================================================
 // IoU / ignore-overlap, float64.  One thread per (n,k) pair; consecutive lanes walk k so the
 // (N,K) row-major store is coalesced and the 32-byte box of row n is a wave-broadcast load.
 // HBM-bound: 32*(N+K) bytes in, 8*N*K bytes out.
 // ============================================================================================
-__device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
-
-// bbox.pyx:17-57 (mode 0) / :59-95 (mode 1); b = box, q = query box.
-__device__ __forceinline__ double overlap_f64(const double b0, const double b1, const double b2, const double b3,
-                                              const double q0, const double q1, const double q2, const double q3,
-                                              const int mode) {
-  const double box_area = (q2 - q0 + 1) * (q3 - q1 + 1);
-  const double iw = dmin(b2, q2) - dmax(b0, q0) + 1;
-  if (iw > 0) {
-    const double ih = dmin(b3, q3) - dmax(b1, q1) + 1;
-    if (ih > 0) {
-      if (mode == 0) {
-        const double ua = (b2 - b0 + 1) * (b3 - b1 + 1) + box_area - iw * ih;
-        return iw * ih / ua;
-      }
-      return iw * ih / box_area;
-    }
-  }
-  return 0.0;
-}
-
 __global__ __launch_bounds__(256) void iou_f64_kernel(const double *__restrict__ boxes, int N,
                                                       const double *__restrict__ query, int K,
                                                       double *__restrict__ out, int mode) {

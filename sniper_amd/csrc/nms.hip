@@ -13,18 +13,9 @@
 //   * batched over images (the proposal op runs it for every chip of the minibatch in one launch).
 // float32 arithmetic identical to devIoU (nms_kernel.cu:24-32): compiled with -ffp-contract=off.
 #include "common.h"
+#include "box_overlap.h"
 
 #include <stdlib.h>
-
-__device__ __forceinline__ float dev_iou(const float *a, const float *b) {
-  const float left = fmaxf(a[0], b[0]), right = fminf(a[2], b[2]);
-  const float top = fmaxf(a[1], b[1]), bottom = fminf(a[3], b[3]);
-  const float width = fmaxf(right - left + 1, 0.f), height = fmaxf(bottom - top + 1, 0.f);
-  const float interS = width * height;
-  const float Sa = (a[2] - a[0] + 1) * (a[3] - a[1] + 1);
-  const float Sb = (b[2] - b[0] + 1) * (b[3] - b[1] + 1);
-  return interS / (Sa + Sb - interS);
-}
 
 // grid = (col_blocks, row_blocks, B), block = 64 (one wave).
 __global__ __launch_bounds__(64) void nms_mask_kernel(const float *__restrict__ boxes, const int32_t *__restrict__ n_per,
