@@ -511,6 +511,92 @@ int sn_coco_accumulate(const double *dt, const int32_t *dt_off, const int32_t *k
                        int max_kept_per_category, long NK, long NG, void *ws, size_t ws_bytes, double *precision, double *recall,
                        sn_stream_t stream);
 
+/* COCO mask evaluation (cocoeval.py with useSegm = 1; the arithmetic of lib/dataset/pycocotools/maskApi.c: rleArea :72-75, rleToBbox
+ * :111-124, rleIou :77-96 behind the bbIou gate of :98-109).  Integer counts and one float64 division per IoU: the matrices are the
+ * reference's bits.  A MASK is a run of u32 counts in column-major order, zeros first (the first count may be 0); the N masks of a call
+ * lie in one pool behind (N+1) i32 prefix offsets, with their sizes in hw (N,2) i32 = h, w.  All tensors are device pointers except
+ * h_out5.  PRECONDITIONS, not checked on the device: every h and w is >= 1; the counts of a mask sum to h * w; only the first count of a
+ * mask is 0 (what rleEncode, rleFrPoly and rleMerge produce; the reference's own walk stops early where two masks have an empty run at
+ * the same position); the masks of a problem share their image's size (the caller compares them on the host); scores are finite.
+ * sn_rle_stats, one launch, a wave per mask:
+ *   rows6  (N,6) f64      x, y, w, h of rleToBbox (run END POINTS only, t = cc - j % 2, an odd last count dropped, an empty mask gives
+ *                         four zeros), score[n] (0 where score is NULL), rleArea -- the rows sn_coco_match_iou and sn_coco_accumulate read
+ *   cum2   (total,2) u32  per run: its end position and the 1-pixels up to and including it (what sn_rle_iou searches)
+ *   total_runs = rle_off[N], max_hw = the largest h * w: known to the caller from building the pool, checked against 32-bit indexing.
+ * sn_rle_iou, one launch, a wave per pair: iou (n_pairs) f64, problem p's D_p x G_p matrix at iou_off[p] (iou_off (P+1) i32,
+ *   iou_off[p+1] - iou_off[p] = D_p * G_p), detection-major in arrival order.  An entry is 0 unless the two rleToBbox boxes overlap with
+ *   positive width and height (bbIou > 0: NOT an optimisation -- a run that wraps into the next column makes rleToBbox understate the
+ *   y-extent, and two masks that intersect can score 0); otherwise i / u with i the common 1-pixels and u = area_d + area_g - i, or
+ *   u = area_d for a crowd (gt_flags bit 0); i = 0 gives 0.  The problems of a call may be a slice of a longer list: row r of dt_off /
+ *   gt_off names mask r - dt_off[0] / r - gt_off[0] of the pools, rows and flags passed with it.
+ * sn_coco_match_iou: sn_coco_match with the IoU of (detection d, box g) of problem p read from iou[iou_off[p] + d * G_p + g] instead of
+ *   computed from boxes; gt_area (NG) f64 replaces the box rows; outputs, tie rules and limits are those of sn_coco_match, and
+ *   sn_coco_accumulate takes them as they are.  Offsets are absolute row numbers of dt / gt_area / gt_flags and the outputs.
+ * Refused before any launch, by a message that names the function and the condition: a NULL tensor; N or P below 1; h * w, the runs or
+ * the pairs of a call past 32-bit indexing; T or A outside SN_COCO_MAX_T / _A; max_det < 1; a problem with more than SN_COCO_MAX_DT
+ * detections or SN_COCO_MAX_GT masks of ground truth; A * T * NK or A * T * NG past 32 bits.  No workspace is needed.
+ * sn_rle_limits: h_out5 (HOST) = {MAX_DT, MAX_GT, runs per scan step of sn_rle_stats and 1-runs per search step of sn_rle_iou (a wave),
+ * masks / pairs per workgroup, threads per workgroup}; the last is also the workgroup of the polygon and paste kernels of mask_rle.hip:
+ * boundary points, crossings and box columns per round of their block scans.  No atomics, no host read-back, the same bits every run. */
+int sn_rle_limits(int32_t *h_out5);
+/* The paste of mask probabilities into the image (mask_voc2coco, lib/mask/mask_voc2coco.py:39-49): detection i has an (M, M) f32 mask
+ * and an i32 box x1, y1, x2, y2 (boxes (n,4): clipped to its image and rounded ON THE HOST, numpy float64, so that 0 <= x1 <= x2 < w and
+ * 0 <= y1 <= y2 < h -- PRECONDITION, not checked on the device); hw (n,2) i32 its image's h, w; col_off (n+1) i32 the prefix of the box
+ * widths x2 - x1 + 1.  The mask is resized to the box, compared >= binary_thresh (float32), zeros outside the box, and the whole image
+ * is run-length encoded column-major (what rleEncode gives for that bitmap).  THE RESIZE IS SPECIFIED BY THIS PROJECT AND NOT PINNED TO
+ * OPENCV: the float32 INTER_LINEAR path of the algorithm oracle/cv_resize.py documents for uint8 -- per axis scale = 1 / (b / M) in
+ * double, coefficient f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; x clamps at both ends (s < 0: s = 0, f = 0;
+ * s >= M - 1: the value is S[M - 1]); y clips its two source rows to [0, M - 1] and keeps the coefficient; horizontal pass S[s] * (1 - f)
+ * + S[s + 1] * f, then the vertical pass, in float32 without fused multiply-add; when both scales are exactly 2 the value is the area
+ * average (((a + b) + c) + d) * 0.25f of the 2 x 2 block.
+ * sn_rle_paste_count, one launch, a workgroup per detection: col_pre (total_cols) i32 = value changes before each box column, det_t
+ *   (n) i32 = value changes per detection.  The caller reads det_t back -- the one read-back of this stage -- and builds rle_off (n+1)
+ *   i32 with det_t[i] + 1 counts per detection.  sn_rle_paste, one launch: tpos (total_runs) u32 workspace, cnts (total_runs) u32.
+ * Refused before any launch: a NULL tensor; n < 1; M outside [1, 1024] or n * M * M past 31 bits; columns or runs past 32-bit
+ * indexing; h * w outside [1, 2^31). */
+int sn_rle_paste_count(const float *masks, const int32_t *boxes, const int32_t *hw, const int32_t *col_off, int n, int M,
+                       float binary_thresh, long total_cols, long max_hw, int32_t *col_pre, int32_t *det_t, sn_stream_t stream);
+int sn_rle_paste(const float *masks, const int32_t *boxes, const int32_t *hw, const int32_t *col_off, const int32_t *col_pre,
+                 const int32_t *rle_off, int n, int M, float binary_thresh, long total_cols, long total_runs, long max_hw,
+                 uint32_t *tpos, uint32_t *cnts, sn_stream_t stream);
+/* Polygons to masks: rleFrPoly (maskApi.c:139-179) per polygon, then the union of an annotation's parts (rleMerge, intersect = 0), on the
+ * reference's counts.  xy (total_vertices,2) f64; poly_off (NP+1) i32 over vertices; poly_hw (NP,2) i32 = h, w of the polygon's image
+ * (the parts of an annotation share it); ann_off (NA+1) i32 over polygons.  edge_pt_off (total_vertices+1) i32: prefix of the edges'
+ * boundary-point counts max(|dx|, |dy|) + 1 of the 5x upsampled integer vertices (int)(5 * x + .5), edge e of a polygon running from its
+ * vertex e to the next (the last back to the first); the caller builds it from the same float64 arithmetic, because it sizes the walk.
+ * sn_rle_poly_cross, one launch, a workgroup per polygon: the boundary walk in closed form per point, float64 with the C casts that
+ *   truncate toward zero, the x-change filter floor(xd) != xd || xd < 0 || xd > w - 1, the yd clamp to [0, h] and ceil.  With
+ *   cross_off = NULL it counts: cross_count (NP) i32 = the kept points x * h + y below h * w (a point AT h * w shares the end with the
+ *   reference's sentinel and never ends a run).  The caller reads the counts back -- the one read-back of this stage --, builds
+ *   cross_off (NP+1) i32 and calls again: cross (total_cross) u32 in boundary order.  A zero-length edge (a repeated or an explicit
+ *   closing vertex) has s = 0 / 0 in the reference, whose v is never read; it is not formed here.
+ * sn_rle_from_polys, two launches: per polygon the distinct positions of odd multiplicity in ascending order -- what the reference's
+ *   sort and sequential compaction leave: odd toggles, even cancels -- found by counting, without a sort (no LDS path, no size at which
+ *   another path takes over; quadratic in the crossings of one polygon), written as counts; then per annotation a copy (one part) or
+ *   the canonical RLE of the OR of the parts.  Pools with slack: polygon p's counts at part_runs[cross_off[p] + p ..), part_m[p] of
+ *   them (at most its crossings + 1); annotation a's at runs[cross_off[q] + q ..) with q = ann_off[a], ann_m[a] of them.
+ * There is no cap on vertices, boundary points or crossings beyond 32-bit indexing.  PRECONDITIONS, not checked on the device: finite
+ * vertices with |5 * x + .5| below 2^31; every annotation has at least one polygon.  Refused before any launch: a NULL tensor; NP or NA
+ * below 1; totals past 32-bit indexing; h * w outside [1, 2^31); a workspace shorter than sn_rle_from_polys_workspace_bytes(total_cross)
+ * (0 for a refused total). */
+int sn_rle_poly_cross(const double *xy, const int32_t *poly_off, const int32_t *edge_pt_off, const int32_t *poly_hw,
+                      const int32_t *cross_off /* or NULL */, int NP, long total_vertices, long total_points, long max_hw,
+                      int32_t *cross_count, uint32_t *cross, sn_stream_t stream);
+size_t sn_rle_from_polys_workspace_bytes(long total_cross);
+int sn_rle_from_polys(const uint32_t *cross, const int32_t *cross_off, const int32_t *poly_hw, const int32_t *ann_off, int NP, int NA,
+                      long total_cross, void *ws, size_t ws_bytes, uint32_t *part_runs, int32_t *part_m, uint32_t *runs, int32_t *ann_m,
+                      sn_stream_t stream);
+int sn_rle_stats(const uint32_t *cnts, const int32_t *rle_off, const int32_t *hw, const double *score /* or NULL */, long N,
+                 long total_runs, long max_hw, double *rows6, uint32_t *cum2, sn_stream_t stream);
+int sn_rle_iou(const uint32_t *dt_cum2, const int32_t *dt_rle_off, const double *dt_rows6, const uint32_t *gt_cum2,
+               const int32_t *gt_rle_off, const double *gt_rows6, const uint8_t *gt_flags, const int32_t *dt_off, const int32_t *gt_off,
+               const int32_t *iou_off, int P, long n_pairs, double *iou, sn_stream_t stream);
+int sn_coco_match_iou(const double *dt, const int32_t *dt_off, const int32_t *kp_off, const double *gt_area, const uint8_t *gt_flags,
+                      const int32_t *gt_off, const double *iou, const int32_t *iou_off, const double *iou_thrs, const double *area_rng,
+                      int P, int T, int A, int max_det, int max_dt_per_problem, int max_gt_per_problem, long NK, long NG,
+                      int32_t *dt_rank, int32_t *dt_match, uint8_t *dt_ignore, int32_t *gt_match, uint8_t *gt_ignore,
+                      sn_stream_t stream);
+
 /* PASCAL VOC box evaluation (lib/dataset/pascal_voc_eval.py:116-181 voc_eval, :39-70 voc_ap).  float64 and integer counts
  * throughout: `rec`, `prec` and `ap07` are the reference's bits, `ap_area` is its sum in another order (each term >= 0, every partial
  * sum <= 1: within (n - 1) * 2^-53 of the exact sum for n recall changes).  A PROBLEM is one (class, image) pair with at least one

@@ -31,6 +31,8 @@ EXTRA = {
     "host_inference.cpp": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
+    "coco_segm.hip": ["-ffp-contract=off"],
+    "mask_rle.hip": ["-ffp-contract=off"],
     "voc_eval.hip": ["-ffp-contract=off"],
     "prop_roidb.hip": ["-ffp-contract=off"],
 }

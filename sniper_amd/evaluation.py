@@ -13,6 +13,9 @@ fallback: without the kernel library or a GPU, evaluate() raises.
 The reference's second data set, PASCAL VOC, ends in the same line through voc_eval / voc_ap: evaluate_detections_voc and
 VOCBoxEvaluator in the second half of this file (sn_voc_match / sn_voc_accumulate, sniper_amd/csrc/voc_eval.hip, DESIGN.md
 section 20).
+
+COCO masks (`imdb.evaluate_sds`, COCOeval with useSegm = 1) from run-length encoded masks: COCOSegmEvaluator at the end of this
+file (sn_rle_stats / sn_rle_iou / sn_coco_match_iou, sniper_amd/csrc/coco_segm.hip).
 """
 import numpy as np
 
@@ -20,7 +23,8 @@ __all__ = ['Params', 'COCOBoxEvaluator', 'COCOBoxResult', 'evaluate_detections',
 
 
 class Params(object):
-    """The reference's Params (cocoeval.py:436-445).  useSegm and useCats = 0 are not implemented."""
+    """The reference's Params (cocoeval.py:436-445).  useSegm belongs to COCOSegmEvaluator (COCOBoxEvaluator refuses it); useCats = 0
+    is not implemented."""
 
     def __init__(self):
         self.iouThrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
@@ -488,3 +492,429 @@ def evaluate_detections_voc(all_boxes, roidb, num_classes, class_names=None, yea
     VOCBoxEvaluator.from_roidb on difficult objects), detections as Tester.aggregate / imdb_detection_wrapper return them ->
     VOCBoxResult; print(result.summary()) gives the reference's lines"""
     return VOCBoxEvaluator.from_roidb(roidb, num_classes, class_names, year).evaluate(all_boxes)
+
+
+# ---- COCO masks ----------------------------------------------------------------------------------------
+# The reference ends a mask run in imdb.evaluate_sds(all_boxes, all_masks) (lib/dataset/coco.py:264-336): COCOeval with useSegm = 1
+# over run-length encoded masks, the arithmetic of lib/dataset/pycocotools/maskApi.c.  sn_rle_stats (rleArea, rleToBbox), sn_rle_iou
+# (rleIou behind its bounding-box gate) and sn_coco_match_iou do the per-image part, sn_coco_accumulate the curves, unchanged
+# (sniper_amd/csrc/coco_segm.hip, DESIGN.md section 22).  The host decodes string counts, builds the pools and the offsets, and cuts
+# the problems into chunks of bounded device memory.
+__all__ += ['COCOSegmEvaluator', 'COCOSegmResult', 'evaluate_sds', 'rle_from_string', 'rle_counts', 'rle_from_polys', 'rle_paste', 'paste_boxes']
+
+
+def rle_from_string(s):
+    """rleFrString (maskApi.c:195-208): compressed string counts -> uint32 counts.  Six bits per character from chr(48): five of
+    payload, 0x20 = another character follows, 0x10 of the last one = the sign; from the third count on the value is a difference
+    to the count two before."""
+    if isinstance(s, bytes):
+        s = s.decode('ascii')
+    cnts, p, n = [], 0, len(s)
+    while p < n:
+        x, k, more = 0, 0, True
+        while more:
+            if p >= n:
+                raise ValueError('rle_from_string: the string ends inside a count')
+            c = ord(s[p]) - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x & 0xFFFFFFFF)
+    return np.array(cnts, np.uint32)
+
+
+def rle_counts(seg, h, w, what):
+    """one RLE `segmentation` entry -> its uint32 counts: {'size': [h, w], 'counts': list | array (uncompressed) | str (compressed)}.
+    ValueError, naming `what`, where the size is not the image's or the counts do not sum to h * w."""
+    if not isinstance(seg, dict) or 'counts' not in seg:
+        raise ValueError('%s: a run-length encoded mask is a dict with `size` and `counts`, got %s' % (what, type(seg).__name__))
+    if 'size' in seg and (int(seg['size'][0]), int(seg['size'][1])) != (int(h), int(w)):
+        raise ValueError('%s: the mask is %d x %d, its image %d x %d' % (what, seg['size'][0], seg['size'][1], h, w))
+    c = seg['counts']
+    if isinstance(c, (str, bytes)):
+        cnts = rle_from_string(c)
+    else:
+        raw = np.asarray(c).reshape(-1)
+        if raw.size and (raw.dtype.kind not in 'iu' or raw.min() < 0 or raw.max() > 0xFFFFFFFF):
+            raise ValueError('%s: counts are non-negative integers below 2^32' % what)
+        cnts = raw.astype(np.uint32)
+    if int(cnts.sum(dtype=np.int64)) != int(h) * int(w):
+        raise ValueError('%s: the counts sum to %d, the image has %d x %d = %d pixels' % (what, int(cnts.sum(dtype=np.int64)), h, w, int(h) * int(w)))
+    if len(cnts) > 1 and not cnts[1:].all():
+        raise ValueError('%s: an empty run after the first count (the reference\'s own walk stops early on such a mask)' % what)
+    return cnts
+
+
+def rle_from_polys(polys, hw, names=None):
+    """rleFrPoly + rleMerge (maskApi.c:139-179, 49-70; cocoeval.py:92-101) on the device: polys[a] = the flat [x0, y0, x1, y1, ...]
+    polygons of annotation a, hw (NA,2) its image's h, w -> one uint32 count array per annotation, the reference's.  The host builds
+    the offsets -- the upsampled integer vertices and the boundary points per edge, in the same float64 arithmetic as the kernel,
+    because they size the walk -- and reads the crossing counts back once (sn_rle_poly_cross, sn_rle_from_polys)."""
+    import torch
+    from . import hip
+    NA = len(polys)
+    names = names or ['rle_from_polys: annotation %d' % a for a in range(NA)]
+    hw = np.asarray(hw, np.int64).reshape(NA, 2)
+    parts, per_ann = [], []
+    for a, ann in enumerate(polys):
+        if not isinstance(ann, (list, tuple)) or len(ann) == 0:
+            raise ValueError('%s: a polygon annotation is a non-empty list of flat coordinate lists' % names[a])
+        for q in ann:
+            q = np.asarray(q, np.float64).reshape(-1)
+            if len(q) < 2 or len(q) % 2 or not np.isfinite(q).all() or np.abs(q).max() >= 2.0 ** 28:
+                raise ValueError('%s: a polygon is x0, y0, x1, y1, ... with at least one vertex, finite and below 2^28 in size' % names[a])
+            parts.append(q.reshape(-1, 2))
+        per_ann.append(len(ann))
+    if hw.min() < 1 or (hw[:, 0] * hw[:, 1]).max() >= 2 ** 31:
+        raise ValueError('rle_from_polys: every image needs h >= 1, w >= 1 and h * w < 2^31')
+    dev = hip.require_gpu()                   # (after the checks: a malformed annotation is reported without a device)
+    NP = len(parts)
+    ann_off = np.concatenate([[0], np.cumsum(per_ann)])
+    poly_off = np.concatenate([[0], np.cumsum([len(q) for q in parts])])
+    xy = np.concatenate(parts)
+    TV = len(xy)
+    xi = np.trunc(5.0 * xy + 0.5).astype(np.int64)            # the C cast (int): truncation toward zero
+    nxt = np.arange(1, TV + 1)
+    nxt[poly_off[1:] - 1] = poly_off[:-1]                     # the last vertex of a polygon is joined to its first
+    d = np.abs(xi[nxt] - xi)
+    edge_pt_off = np.concatenate([[0], np.cumsum(np.maximum(d[:, 0], d[:, 1]) + 1)])
+    if edge_pt_off[-1] >= 2 ** 31 or TV >= 2 ** 30:
+        raise ValueError('rle_from_polys: %d boundary points and %d vertices in one call, 32-bit indexing takes fewer' % (edge_pt_off[-1], TV))
+    poly_hw = np.repeat(hw, per_ann, axis=0).astype(np.int32)
+    max_hw = int((hw[:, 0] * hw[:, 1]).max())
+    i32 = lambda n: torch.empty([max(int(n), 1)], dtype=torch.int32, device=dev)
+    d_xy, d_poly_off, d_edge, d_hw = hip.dev(xy), hip.dev(poly_off.astype(np.int32)), hip.dev(edge_pt_off.astype(np.int32)), hip.dev(poly_hw)
+    count = i32(NP)
+    hip.call('sn_rle_poly_cross', d_xy, d_poly_off, d_edge, d_hw, None, NP, TV, int(edge_pt_off[-1]), max_hw, count, None, hip.stream())
+    cross_off = np.concatenate([[0], np.cumsum(count[:NP].cpu().numpy().astype(np.int64))])
+    total = int(cross_off[-1])
+    if total + NP >= 2 ** 30:
+        raise ValueError('rle_from_polys: %d crossings in one call, 32-bit indexing takes fewer' % total)
+    d_cross_off, cross = hip.dev(cross_off.astype(np.int32)), i32(total)
+    hip.call('sn_rle_poly_cross', d_xy, d_poly_off, d_edge, d_hw, d_cross_off, NP, TV, int(edge_pt_off[-1]), max_hw, None, cross, hip.stream())
+    ws = torch.empty(int(hip.query('sn_rle_from_polys_workspace_bytes', total)), dtype=torch.uint8, device=dev)
+    part_runs, runs, part_m, ann_m = i32(total + NP), i32(total + NP), i32(NP), i32(NA)
+    hip.call('sn_rle_from_polys', cross, d_cross_off, d_hw, hip.dev(ann_off.astype(np.int32)), NP, NA, total, ws, ws.numel(), part_runs,
+             part_m, runs, ann_m, hip.stream())
+    h_runs, h_m = runs.cpu().numpy().view(np.uint32), ann_m[:NA].cpu().numpy()
+    start = cross_off[ann_off[:-1]] + ann_off[:-1]
+    return [h_runs[start[a]:start[a] + h_m[a]].copy() for a in range(NA)]
+
+
+def paste_boxes(rows, h, w, what='paste_boxes'):
+    """The box of mask_voc2coco for every detection row (x1, y1, x2, y2, ...): clip_boxes (lib/bbox/bbox_transform.py:35-50) in float64,
+    then np.round(...).astype(int) -> (n,4) int.  A box with x2 < x1 or y2 < y1 after that is refused with a ValueError that names
+    the detection (the reference's cv2.resize fails on it too)."""
+    b = np.array(np.asarray(rows)[:, :4], np.float64).reshape(-1, 4)
+    b[:, 0::2] = np.maximum(np.minimum(b[:, 0::2], w - 1), 0)
+    b[:, 1::2] = np.maximum(np.minimum(b[:, 1::2], h - 1), 0)
+    b = np.round(b).astype(int)
+    bad = np.flatnonzero((b[:, 2] < b[:, 0]) | (b[:, 3] < b[:, 1]))
+    if len(bad):
+        raise ValueError('%s: detection %d has the box %s after clipping and rounding: x2 < x1 or y2 < y1' % (what, bad[0], b[bad[0]].tolist()))
+    return b
+
+
+def rle_paste(masks, boxes, hw, binary_thresh=0.4):
+    """mask_voc2coco (lib/mask/mask_voc2coco.py:39-49) on the device: masks (n, M, M) probabilities, boxes (n,4) int from paste_boxes,
+    hw (n,2) each detection's image size -> one uint32 count array per detection: the mask resized to its box (float32 bilinear, the
+    resize this project specifies -- include/sniper_hip.h -- NOT pinned to OpenCV), >= float32(binary_thresh), zeros outside the box,
+    the whole image run-length encoded column-major.  One read-back: the value changes per detection (sn_rle_paste_count, sn_rle_paste)."""
+    import torch
+    from . import hip
+    dev = hip.require_gpu()
+    masks = np.ascontiguousarray(masks, np.float32)
+    n, M = masks.shape[0], masks.shape[1]
+    assert masks.shape == (n, M, M) and n >= 1, 'masks are (n, M, M)'
+    boxes = np.ascontiguousarray(boxes, np.int32).reshape(n, 4)
+    hw = np.ascontiguousarray(hw, np.int32).reshape(n, 2)
+    ok = (0 <= boxes[:, 0]) & (boxes[:, 0] <= boxes[:, 2]) & (boxes[:, 2] < hw[:, 1]) & (0 <= boxes[:, 1]) & (boxes[:, 1] <= boxes[:, 3]) & (boxes[:, 3] < hw[:, 0])
+    if not ok.all():
+        raise ValueError('rle_paste: detection %d has the box %s outside its %d x %d image or empty' % (
+            np.flatnonzero(~ok)[0], boxes[np.flatnonzero(~ok)[0]].tolist(), hw[np.flatnonzero(~ok)[0], 0], hw[np.flatnonzero(~ok)[0], 1]))
+    col_off = np.concatenate([[0], np.cumsum(boxes[:, 2].astype(np.int64) - boxes[:, 0] + 1)])
+    max_hw = int((hw[:, 0].astype(np.int64) * hw[:, 1]).max())
+    thr = float(np.float32(binary_thresh))
+    i32 = lambda k: torch.empty([max(int(k), 1)], dtype=torch.int32, device=dev)
+    d_m, d_b, d_hw, d_col = hip.dev(masks), hip.dev(boxes), hip.dev(hw), hip.dev(col_off.astype(np.int32))
+    col_pre, det_t = i32(col_off[-1]), i32(n)
+    hip.call('sn_rle_paste_count', d_m, d_b, d_hw, d_col, n, M, thr, int(col_off[-1]), max_hw, col_pre, det_t, hip.stream())
+    rle_off = np.concatenate([[0], np.cumsum(det_t[:n].cpu().numpy().astype(np.int64) + 1)])
+    total = int(rle_off[-1])
+    tpos, cnts = i32(total), i32(total)
+    hip.call('sn_rle_paste', d_m, d_b, d_hw, d_col, col_pre, hip.dev(rle_off.astype(np.int32)), n, M, thr, int(col_off[-1]), total, max_hw,
+             tpos, cnts, hip.stream())
+    h_c = cnts[:total].cpu().numpy().view(np.uint32)
+    return [h_c[rle_off[i]:rle_off[i + 1]].copy() for i in range(n)]
+
+
+class COCOSegmResult(COCOBoxResult):
+    """COCOBoxResult of a mask evaluation: the same arrays, statistics and summary lines (the reference's summary does not name the
+    IoU type); timing names the stages"""
+    iou_type = 'segm'
+
+
+def _pool(rles):
+    off = np.zeros(len(rles) + 1, np.int64)
+    if len(rles):
+        np.cumsum(np.fromiter(map(len, rles), np.int64, len(rles)), out=off[1:])
+    cnts = np.concatenate(rles).astype(np.uint32, copy=False) if off[-1] else np.zeros(0, np.uint32)
+    return cnts, off
+
+
+class COCOSegmEvaluator(object):
+    """gt: dict over the NG annotations in annotation order -- image (index into image_ids), category (index into cat_ids), area (the
+    annotation's own, as in the reference), iscrowd, ignore (optional, 0) and segmentation: per annotation a dict with `size` and
+    `counts` as a list (uncompressed RLE) or as a string (compressed: decoded on the host by rle_from_string), or a polygon list.  image_sizes: (I,2)
+    h, w.  params: a Params (default: the reference's); useSegm is implied.  chunk_elements bounds the device memory of a chunk: the
+    runs of its masks plus the entries of its IoU matrices.
+
+    A segmentation may also be a list of flat polygon coordinate lists: those annotations are converted together on the device
+    (rle_from_polys: rleFrPoly and the union of the parts)."""
+
+    def __init__(self, gt, image_ids, cat_ids, image_sizes, params=None, chunk_elements=1 << 23):
+        self.params = params or Params()
+        if not getattr(self.params, 'useCats', 1):
+            raise NotImplementedError('COCOSegmEvaluator: useCats = 0 (category-agnostic evaluation) is not implemented')
+        self.image_ids, self.cat_ids = list(image_ids), list(cat_ids)
+        I, K = len(self.image_ids), len(self.cat_ids)
+        self.image_sizes = np.asarray(image_sizes, np.int64).reshape(I, 2)
+        if I and (self.image_sizes.min() < 1 or (self.image_sizes[:, 0] * self.image_sizes[:, 1]).max() >= 2 ** 31):
+            raise ValueError('COCOSegmEvaluator: every image needs h >= 1, w >= 1 and h * w < 2^31')
+        self.chunk_elements = int(chunk_elements)
+        n = len(gt['image'])
+        self.gt = {
+            'image': np.asarray(gt['image'], np.int64).reshape(n), 'category': np.asarray(gt['category'], np.int64).reshape(n),
+            'area': np.asarray(gt['area'], np.float64).reshape(n), 'iscrowd': np.asarray(gt['iscrowd']).reshape(n).astype(np.int64) != 0,
+            'ignore': (np.asarray(gt['ignore']).reshape(n).astype(np.int64) != 0) if 'ignore' in gt else np.zeros(n, bool),
+        }
+        assert n == 0 or (0 <= self.gt['image'].min() and self.gt['image'].max() < I), 'gt image index out of range'
+        assert n == 0 or (0 <= self.gt['category'].min() and self.gt['category'].max() < K), 'gt category index out of range'
+        assert len(gt['segmentation']) == n, '%d segmentations for %d annotations' % (len(gt['segmentation']), n)
+        self.gt_rle = []
+        for a, seg in enumerate(gt['segmentation']):
+            h, w = self.image_sizes[self.gt['image'][a]]
+            if isinstance(seg, (list, tuple)):
+                self.gt_rle.append(None)              # polygons: converted together on the device, below
+            else:
+                self.gt_rle.append(rle_counts(seg, h, w, 'COCOSegmEvaluator: annotation %d' % a))
+        poly = [a for a, r in enumerate(self.gt_rle) if r is None]
+        if poly:
+            rles = rle_from_polys([gt['segmentation'][a] for a in poly], self.image_sizes[self.gt['image'][poly]],
+                                  ['COCOSegmEvaluator: annotation %d' % a for a in poly])
+            for a, r in zip(poly, rles):
+                self.gt_rle[a] = r
+
+    @classmethod
+    def from_roidb(cls, roidb, num_classes, params=None, **kw):
+        """Ground truth = the roidb rows with gt_classes > 0: the mask of row j is roidb[i]['gt_masks'][j] (the polygon lists of
+        the training roidb, or an RLE dict), the image size roidb[i]['height'] / ['width'], area =
+        roidb[i]['gt_areas'] where present, else the mask's rleArea from the device (sn_rle_stats), iscrowd = roidb[i]['gt_iscrowd']
+        where present, else 0.  Image ids are 1.., category ids 1..num_classes-1, annotation ids follow the roidb order."""
+        img, cat, area, crowd, seg = [], [], [], [], []
+        for i, r in enumerate(roidb):
+            classes = np.asarray(r['gt_classes'])
+            keep = np.flatnonzero(classes > 0)
+            img.append(np.full(len(keep), i, np.int64))
+            cat.append(classes[keep].astype(np.int64) - 1)
+            area.append(np.asarray(r['gt_areas'], np.float64)[keep] if 'gt_areas' in r else np.full(len(keep), np.nan))
+            crowd.append(np.asarray(r['gt_iscrowd'])[keep].astype(np.int64) if 'gt_iscrowd' in r else np.zeros(len(keep), np.int64))
+            seg.extend(r['gt_masks'][j] for j in keep)
+        cat0 = lambda parts, dt: np.concatenate(parts) if parts else np.zeros((0,), dt)
+        gt = {'image': cat0(img, np.int64), 'category': cat0(cat, np.int64), 'area': cat0(area, np.float64), 'iscrowd': cat0(crowd, np.int64),
+              'segmentation': seg}
+        ev = cls(gt, range(1, len(roidb) + 1), range(1, num_classes), [(r['height'], r['width']) for r in roidb], params, **kw)
+        missing = np.flatnonzero(np.isnan(ev.gt['area']))
+        if len(missing):
+            ev.gt['area'][missing] = ev.mask_areas([ev.gt_rle[n] for n in missing], ev.image_sizes[ev.gt['image'][missing]])
+        return ev
+
+    @staticmethod
+    def mask_areas(rles, hw):
+        """rleArea of every mask, on the device (sn_rle_stats) -> (N) float64"""
+        import torch
+        from . import hip
+        dev = hip.require_gpu()
+        cnts, off = _pool(rles)
+        hw = np.asarray(hw, np.int64).reshape(len(rles), 2)
+        rows = torch.empty((len(rles), 6), dtype=torch.float64, device=dev)
+        cum = torch.empty((max(int(off[-1]), 1), 2), dtype=torch.int32, device=dev)
+        d_c = hip.dev(cnts.view(np.int32)) if len(cnts) else torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.call('sn_rle_stats', d_c, hip.dev(off.astype(np.int32)), hip.dev(hw.astype(np.int32)), None, len(rles), int(off[-1]),
+                 int((hw[:, 0] * hw[:, 1]).max()), rows, cum, hip.stream())
+        return rows[:, 5].cpu().numpy()
+
+    # ---- detections -----------------------------------------------------------------------------
+    def convert_detections(self, all_boxes, all_masks, binary_thresh=0.4):
+        """-> (scores (ND) float64, UNROUNDED as coco.py:57 leaves them for segm; the masks' counts, one uint32 array per detection; the
+        (K, I) row counts), all in class-major, image, row order -- the order of the reference's result list.  A cell of all_masks is
+        the (n, M, M) probabilities of the cell's boxes -- pasted on the device, all cells of one M in one rle_paste call -- or a list
+        of n RLE dicts, taken as they are."""
+        K, I = len(self.cat_ids), len(self.image_ids)
+        counts = _cell_counts(all_boxes, K, I)
+        assert len(all_masks) == K + 1, 'all_masks[class][image]: %d classes (with the background) for %d categories' % (len(all_masks), K)
+        scores, rles, pending = [], [], {}
+        for k in range(K):
+            assert len(all_masks[k + 1]) == I, 'all_masks[%d] has %d images, the ground truth %d' % (k + 1, len(all_masks[k + 1]), I)
+            for i in np.flatnonzero(counts[k]):
+                rows, cell = all_boxes[k + 1][i], all_masks[k + 1][i]
+                rows = np.asarray(rows.cpu() if hasattr(rows, 'cpu') else rows).reshape(-1, 5)
+                if len(cell) != len(rows):
+                    raise ValueError('COCOSegmEvaluator: all_masks[%d][%d] has %d masks, all_boxes[%d][%d] %d rows' % (k + 1, i, len(cell), k + 1, i, len(rows)))
+                h, w = self.image_sizes[i]
+                scores.append(rows[:, 4].astype(np.float64))
+                if isinstance(cell, (list, tuple)):
+                    rles.extend(rle_counts(seg, h, w, 'COCOSegmEvaluator: detection %d of all_masks[%d][%d]' % (n, k + 1, i)) for n, seg in enumerate(cell))
+                    continue
+                prob = np.asarray(cell.cpu() if hasattr(cell, 'cpu') else cell)
+                if prob.ndim != 3 or prob.shape[1] != prob.shape[2]:
+                    raise ValueError('COCOSegmEvaluator: all_masks[%d][%d] is neither a list of RLE dicts nor (n, M, M) probabilities' % (k + 1, i))
+                box = paste_boxes(rows, h, w, 'COCOSegmEvaluator: all_boxes[%d][%d]' % (k + 1, i))
+                slot = pending.setdefault(prob.shape[1], ([], [], [], []))
+                slot[0].append(prob.astype(np.float32, copy=False)), slot[1].append(box), slot[2].append(np.tile([[h, w]], (len(rows), 1)))
+                slot[3].extend(range(len(rles), len(rles) + len(rows)))
+                rles.extend([None] * len(rows))
+        for prob, box, hw, where in pending.values():
+            for n, r in zip(where, rle_paste(np.concatenate(prob), np.concatenate(box), np.concatenate(hw), binary_thresh)):
+                rles[n] = r
+        return (np.concatenate(scores) if scores else np.zeros(0)), rles, counts
+
+    def _chunks(self, cost):
+        """problem ranges [p0, p1) whose summed cost stays within chunk_elements (a single problem over it is a chunk of its own)"""
+        cum = np.concatenate([[0], np.cumsum(cost)])
+        out, p0, P = [], 0, len(cost)
+        while p0 < P:
+            p1 = int(np.searchsorted(cum, cum[p0] + self.chunk_elements, side='right')) - 1
+            p1 = min(max(p1, p0 + 1), P)
+            out.append((p0, p1))
+            p0 = p1
+        return out
+
+    def evaluate(self, all_boxes, all_masks, binary_thresh=0.4, return_matches=False, return_rles=False):
+        """all_boxes[class][image] = (n,5) rows x1, y1, x2, y2, score; all_masks[class][image] = a list of n RLE dicts (class 0 =
+        background) or the (n, M, M) mask probabilities of those rows, pasted into the image at binary_thresh (rle_paste)
+        -> COCOSegmResult.
+        return_matches adds result.matches (sn_coco_match_iou's outputs, the offsets, the IoU matrices as iou / iou_off and the
+        rows of sn_rle_stats), return_rles adds result.rles (the counts of every detection and annotation in problem order)."""
+        import torch
+        from . import hip
+        p = self.params
+        dev = hip.require_gpu()
+        iou_thrs, rec_thrs = np.asarray(p.iouThrs, np.float64), np.asarray(p.recThrs, np.float64)
+        area_rng = np.asarray(p.areaRng, np.float64).reshape(-1, 2)
+        max_dets = np.asarray(sorted(p.maxDets), np.int32)
+        T, R, A, M, K = len(iou_thrs), len(rec_thrs), len(area_rng), len(max_dets), len(self.cat_ids)
+        max_det = int(max_dets[-1])
+        t0 = _now(torch)
+        scores, dt_rle, counts = self.convert_detections(all_boxes, all_masks, binary_thresh)
+        ND, NG = len(dt_rle), len(self.gt_rle)
+        pr = _problem_offsets(counts, self.gt['category'], self.gt['image'])
+        pr['kp_off'] = _offsets(np.minimum(pr.pop('dt_counts'), max_det))
+        P = pr['P']
+        if P == 0:                                    # nothing to evaluate: every category is absent
+            return COCOSegmResult(-np.ones((T, R, K, A, M)), -np.ones((T, K, A, M)), p, self.cat_ids)
+        lim = np.zeros(5, np.int32)
+        hip.call('sn_rle_limits', lim)
+        if pr['max_dt'] > lim[0] or pr['max_gt'] > lim[1]:          # sn_coco_match_iou would refuse the chunk: say so before any launch
+            raise ValueError('COCOSegmEvaluator: a problem has %d detections and a problem has %d masks of ground truth; '
+                             'sn_coco_match_iou takes at most %d and %d' % (pr['max_dt'], pr['max_gt'], lim[0], lim[1]))
+        NK = int(pr['kp_off'][-1])
+        o = pr['gt_order']
+        gt_rle = [self.gt_rle[n] for n in o]
+        flags = (self.gt['iscrowd'][o].astype(np.uint8) | (self.gt['ignore'][o].astype(np.uint8) << 1)) if NG else np.zeros(1, np.uint8)
+        gt_area = self.gt['area'][o] if NG else np.zeros(1)
+        kk, ii = np.nonzero(counts)
+        dt_hw = np.repeat(self.image_sizes[ii], counts[kk, ii], axis=0).astype(np.int32).reshape(-1, 2)
+        gt_hw = self.image_sizes[self.gt['image'][o]].astype(np.int32).reshape(-1, 2)
+        d_cnts, d_roff = _pool(dt_rle)
+        g_cnts, g_roff = _pool(gt_rle)
+        dt_off, gt_off = pr['dt_off'].astype(np.int64), pr['gt_off'].astype(np.int64)
+        pairs = np.diff(dt_off) * np.diff(gt_off)
+        chunks = self._chunks(np.diff(d_roff[dt_off]) + np.diff(g_roff[gt_off]) + pairs)
+        kept_per_cat = np.diff(pr['kp_off'][pr['cat_off']].astype(np.int64))
+        t1 = _now(torch)
+        empty = lambda dtype, *shape: torch.empty([max(int(np.prod(shape)), 1)], dtype=dtype, device=dev)
+        d_dt, d_gt = torch.zeros((max(ND, 1), 6), dtype=torch.float64, device=dev), torch.zeros((max(NG, 1), 6), dtype=torch.float64, device=dev)
+        d_area, d_flags = hip.dev(gt_area), hip.dev(flags)
+        d_dt_off, d_gt_off, d_kp_off, d_cat_off = (hip.dev(pr[k]) for k in ('dt_off', 'gt_off', 'kp_off', 'cat_off'))
+        d_iou_thr, d_rec, d_rng = hip.dev(iou_thrs), hip.dev(rec_thrs), hip.dev(area_rng)
+        dt_rank, dt_match, dt_ignore = empty(torch.int32, NK), empty(torch.int32, A, T, NK), empty(torch.uint8, A, T, NK)
+        gt_match, gt_ignore = empty(torch.int32, A, T, NG), empty(torch.uint8, A, NG)
+        precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+        recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(hip.query('sn_coco_accumulate_workspace_bytes', NK, T, A)), dtype=torch.uint8, device=dev)
+        tm = {'host_s': t1 - t0, 'upload_s': _now(torch) - t1, 'stats_s': 0., 'iou_s': 0., 'match_s': 0.}
+        ious, iou_offs = [], [np.zeros(1, np.int64)]
+
+        def upload(cnts, roff, hw, lo, hi, score):
+            """masks [lo, hi) of a pool -> the device operands of sn_rle_stats (counts, relative run offsets, sizes, scores, cum2)"""
+            if hi == lo:
+                return None
+            rel = (roff[lo:hi + 1] - roff[lo]).astype(np.int32)
+            total = int(rel[-1])
+            d_c = hip.dev(cnts[roff[lo]:roff[hi]].view(np.int32)) if total else empty(torch.int32, 1)
+            return (d_c, hip.dev(rel), hip.dev(hw[lo:hi]), hip.dev(score[lo:hi]) if score is not None else None, hi - lo, total,
+                    int((hw[lo:hi, 0].astype(np.int64) * hw[lo:hi, 1]).max()), empty(torch.int32, total, 2))
+
+        for p0, p1 in chunks:
+            tc = _now(torch)
+            dl, dh, gl, gh = int(dt_off[p0]), int(dt_off[p1]), int(gt_off[p0]), int(gt_off[p1])
+            up_d, up_g = upload(d_cnts, d_roff, dt_hw, dl, dh, scores), upload(g_cnts, g_roff, gt_hw, gl, gh, None)
+            io = np.concatenate([[0], np.cumsum(pairs[p0:p1])])
+            n_pairs = int(io[-1])
+            assert n_pairs < 2 ** 31, 'a chunk has %d (detection, annotation) pairs: lower chunk_elements' % n_pairs
+            d_io, iou = hip.dev(io.astype(np.int32)), empty(torch.float64, n_pairs)
+            tu = _now(torch)
+            for up, rows, lo in ((up_d, d_dt, dl), (up_g, d_gt, gl)):
+                if up is not None:
+                    hip.call('sn_rle_stats', up[0], up[1], up[2], up[3], up[4], up[5], up[6], rows[lo:], up[7], hip.stream())
+            ts = _now(torch)
+            if n_pairs:
+                hip.call('sn_rle_iou', up_d[7], up_d[1], d_dt[dl:], up_g[7], up_g[1], d_gt[gl:], d_flags[gl:], d_dt_off[p0:], d_gt_off[p0:],
+                         d_io, p1 - p0, n_pairs, iou, hip.stream())
+            ti = _now(torch)
+            hip.call('sn_coco_match_iou', d_dt, d_dt_off[p0:], d_kp_off[p0:], d_area, d_flags, d_gt_off[p0:], iou, d_io, d_iou_thr, d_rng,
+                     p1 - p0, T, A, max_det, int(np.diff(dt_off[p0:p1 + 1]).max()), int(np.diff(gt_off[p0:p1 + 1]).max()), NK, NG,
+                     dt_rank, dt_match, dt_ignore, gt_match, gt_ignore, hip.stream())
+            te = _now(torch)
+            tm['upload_s'] += tu - tc
+            tm['stats_s'] += ts - tu
+            tm['iou_s'] += ti - ts
+            tm['match_s'] += te - ti
+            if return_matches:
+                ious.append(iou[:n_pairs].cpu().numpy())
+                iou_offs.append(io[1:] + iou_offs[-1][-1])
+        t2 = _now(torch)
+        hip.call('sn_coco_accumulate', d_dt, d_dt_off, d_kp_off, d_gt_off, d_cat_off, dt_rank, dt_match, dt_ignore, gt_ignore, d_rec,
+                 max_dets, P, K, T, A, M, R, max_det, int(kept_per_cat.max()), NK, NG, ws, ws.numel(), precision, recall, hip.stream())
+        t3 = _now(torch)
+        h_precision, h_recall = precision.cpu().numpy(), recall.cpu().numpy()
+        t4 = _now(torch)
+        # seconds: host = counts of the masks, pools, CSR offsets; upload = allocations + copies to the device (all chunks); stats =
+        # sn_rle_stats, iou = sn_rle_iou, match = sn_coco_match_iou (all chunks); accumulate = sn_coco_accumulate; download = precision
+        # + recall to the host
+        tm.update({'accumulate_s': t3 - t2, 'download_s': t4 - t3, 'kernels_s': tm['stats_s'] + tm['iou_s'] + tm['match_s'] + t3 - t2,
+                   'problems': P, 'detections': ND, 'kept': NK, 'boxes': NG, 'chunks': len(chunks), 'pairs': int(pairs.sum()),
+                   'runs': int(d_roff[-1] + g_roff[-1])})
+        res = COCOSegmResult(h_precision, h_recall, p, self.cat_ids, tm)
+        if return_matches:
+            res.matches = dict(pr, NK=NK, dt_rank=dt_rank[:NK].cpu().numpy(), dt_match=dt_match[:A * T * NK].reshape(A, T, NK).cpu().numpy(),
+                               dt_ignore=dt_ignore[:A * T * NK].reshape(A, T, NK).cpu().numpy(),
+                               gt_match=gt_match[:A * T * NG].reshape(A, T, NG).cpu().numpy(),
+                               gt_ignore=gt_ignore[:A * NG].reshape(A, NG).cpu().numpy(), dt=d_dt[:ND].cpu().numpy(), gt=d_gt[:NG].cpu().numpy(),
+                               iou=np.concatenate(ious) if ious else np.zeros(0), iou_off=np.concatenate(iou_offs))
+        if return_rles:
+            res.rles = {'dt': dt_rle, 'gt': gt_rle}
+        return res
+
+
+def evaluate_sds(all_boxes, all_masks, roidb, num_classes, binary_thresh=0.4, params=None):
+    """`imdb.evaluate_sds(all_boxes, all_masks)` of the reference's mask test run in one call, for run-length encoded masks on both
+    sides: ground truth from the roidb (COCOSegmEvaluator.from_roidb), detections as lists of RLE dicts beside all_boxes ->
+    COCOSegmResult; print(result.summary()) gives the reference's twelve lines"""
+    return COCOSegmEvaluator.from_roidb(roidb, num_classes, params).evaluate(all_boxes, all_masks, binary_thresh=binary_thresh)
