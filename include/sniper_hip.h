@@ -731,6 +731,19 @@ int sn_space_to_depth2(const void *in, void *out, int N, int H, int W, int C, sn
 int sn_pick_fwd(const void *x, const float *index, void *y, int N, int HW, int C, sn_stream_t stream);
 int sn_pick_bwd(const void *dy, const float *index, void *dx, int N, int HW, int C, int accumulate, sn_stream_t stream);
 
+/* Mask head at test time (semantics ours, like the rest of the mask branch): the foreground probability of
+ * every RoI's OWN class from the output of mask_deconv_relu, in one launch -- mask_out's 1x1 convolution restricted to the two maps
+ * the class reads, the two picks, the concatenation and the 2-way softmax of the stock chain.
+ *   x (N, HW, C) fp16 channels-last; w16 (2K, C) fp16, rows [Cout][Cin] (mask_out's compute copy); bias (2K) fp32 or NULL;
+ *   cls (N) fp32 class index per RoI, as sn_pick_fwd takes its index; prob (N, HW) fp32.
+ *   neg = clip((int)cls[n], 0, 2K-1), pos = clip((int)cls[n] + K, 0, 2K-1)            (sn_pick_fwd's clipping on 2K channels)
+ *   z_neg = sum_k x[n,p,k] * w[neg,k] + bias[neg], z_pos likewise: fp16 operands, fp32 accumulation, NOT rounded to fp16
+ *   prob[n,p] = channel 1 of softmax(z_neg, z_pos), max subtracted first, the statements of sn_softmax_fwd for a K = 2 row.
+ * One launch, no atomics, no workspace, no host read-back, the same bits every run.  Refused before any launch: a NULL x, w16,
+ * cls or prob; N, HW, C or K below 1; C not a multiple of 8; N*HW*C past 32-bit indexing; x or w16 not 16-byte aligned. */
+int sn_mask_class_prob(const void *x, const void *w16, const float *bias, const float *cls, float *prob, int N, int HW, int C, int K,
+                       sn_stream_t stream);
+
 /* DeformablePSROIPooling, group_size 1 (:286-293).  data (B,H,W,C) fp16, rois (R,5), trans (R,2,P,P) or NULL,
  * out (R,P,P,C) fp16.  Backward: d_data (B,H,W,C) fp16 (d_data_f32 = 0) or fp32 and d_trans (R,2,P,P) fp32 are
  * OVERWRITTEN (every element written exactly once, no atomics); ws = sn_dpsroi_bwd_workspace_bytes(R). */

@@ -30,6 +30,7 @@ EXTRA = {
     "infer.hip": ["-ffp-contract=off"],
     "host_inference.cpp": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
+    "mask_infer.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
     "coco_segm.hip": ["-ffp-contract=off"],
     "mask_rle.hip": ["-ffp-contract=off"],

@@ -1407,6 +1407,33 @@ class PickStep(Step):
         self.y.grad = None
 
 
+@register('MaskClassProb')
+class MaskClassProbStep(Step):
+    """The mask head's output stage at test time: one sn_mask_class_prob launch in place of mask_out's
+    Convolution -> pick -> pick -> Concat -> SoftmaxActivation.  The weight is registered like a 1x1 convolution's (rows
+    [Cout][Cin]), so a checkpoint's mask_out_weight / mask_out_bias bind unchanged.  Test-time only: there is no backward, the
+    training graph keeps its stock operators."""
+
+    def setup(self):
+        ex = self.ex
+        if ex.for_training:
+            raise NotImplementedError('%s: MaskClassProb is a test-time operator (no backward); the training graph uses '
+                                      'Convolution + pick + SoftmaxOutput' % self.node.name)
+        self.x, self.idx = self.data_in('data'), self.data_in('index')
+        self.K = int(self.a['num_classes'])
+        if len(self.x.shape) != 4 or self.x.fmt != 'act' or tuple(self.idx.shape) != (self.x.shape[0],):
+            raise NotImplementedError('%s: MaskClassProb needs an (N, C, H, W) activation tensor and one index per RoI (got %s, %s)'
+                                      % (self.node.name, self.x.shape, self.idx.shape))
+        self.w = ex.register_param(self.pname('weight'), 'conv', None, need_wT=False)
+        self.b = ex.register_param(self.pname('bias')) if 'bias' in self.slots else None
+        self.y = self.new_out('f32')
+
+    def forward(self):
+        n, h, w, c = self.x.nhwc()
+        hip.call('sn_mask_class_prob', self.x.t, self.w.w16, self.b.master if self.b is not None else None,
+                 self.ex.as_f32(self.idx), self.y.t, n, h * w, c, self.K, hip.stream())
+
+
 @register('DeformablePSROIPooling')
 class DPSROIPoolStep(Step):
     """group_size 1 (the SNIPER heads, :286-293): sn_dpsroi_pool_*; group_size G > 1 (position-sensitive R-FCN head,

@@ -159,7 +159,16 @@ def infer_node(node, ins, shapes_of_var):
         if 'index' in pos and ins[pos['index']] is None:
             par[pos['index']] = tuple(d for i, d in enumerate(x) if i != axis)
         return [out], par
-    if op == 'BoxAnnotatorOHEM':         # box_annotator_ohem.py:103-114: the shapes of `labels` / `bbox_weights`
+    if op == 'MaskClassProb':            # data (N, C, H, W), one class index per RoI -> the class's foreground probability map
+        n, c, h, w = ins[pos['data']]
+        k = int(a['num_classes'])
+        par[pos['weight']] = (2 * k, c, 1, 1)
+        if 'bias' in pos:
+            par[pos['bias']] = (2 * k,)
+        if ins[pos['index']] is None:
+            par[pos['index']] = (n,)
+        return [(n, 1, h, w)], par
+    if op == 'BoxAnnotatorOHEM':        # box_annotator_ohem.py:103-114: the shapes of `labels` / `bbox_weights`
         lab, wgt = tuple(ins[pos['labels']]), tuple(ins[pos['bbox_weights']])
         return [lab, wgt, lab][:node.num_outputs], par
     if op == 'Custom':

@@ -92,6 +92,9 @@ _OPS = {
     'MultiProposalTargetMask': (['cls_prob', 'bbox_pred', 'im_info', 'gt_boxes', 'valid_ranges'], [], 6),
     'MaskRcnnTarget': (['rois', 'mask_polys', 'mask_ids'], [], 2),
     'pick': (['data', 'index'], [], 1),
+    # the mask head's output stage at test time (ours): mask_out's 1x1 convolution restricted to the two maps of
+    # each RoI's class + pick + pick + Concat + SoftmaxActivation(channel)[1] as one operator -> (N, 1, H, W) float32
+    'MaskClassProb': (['data', 'weight', 'bias', 'index'], [], 1),
     # lib/operator_py/box_annotator_ohem.py:86-120 as a native operator (a third output with get_fg_labels: _num_outputs)
     'BoxAnnotatorOHEM': (['cls_score', 'bbox_pred', 'labels', 'bbox_targets', 'bbox_weights'], [], 2),
 }
