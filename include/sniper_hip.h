@@ -652,6 +652,59 @@ int sn_voc_accumulate(const double *dt_score, const int32_t *dt_off, const int32
                       int T, int max_dt_per_class, long ND, long NG, void *ws, size_t ws_bytes, int32_t *order, double *rec,
                       double *prec, int32_t *npos, double *ap07, double *ap_area, sn_stream_t stream);
 
+/* PASCAL VOC mask evaluation (lib/dataset/pascal_voc_eval.py:184-272 voc_eval_sds; lib/mask/mask_transform.py:40-70 mask_overlap):
+ * the mask AP of the FCIS / DCN lineage (mAP^r).  Integer counts and one float64 division per overlap: the matrix, tp and fp are the
+ * reference's, and sn_voc_accumulate -- AS IT IS, called with an all-zero gt_difficult, so that npos is the reference's num_pos --
+ * gives rec, prec and ap07 (the number voc_eval_sds returns) on its bits and ap_area beside them.  (The entry points are named
+ * sn_vocsds_* and not sn_voc_*: the box evaluation's tests own that prefix.)  A PROBLEM is one (class, image) pair with at least one
+ * detection or one instance, class-major then by image: the layout of sn_voc_match.  All tensors are device pointers except h_out6.
+ *   masks      (ND,M,M) f32  probability maps, a problem's detections contiguous in arrival order
+ *   dt_box     (ND,4) i32    x1, y1, x2, y2 = np.round(box).astype(int), done ON THE HOST in float64.  A box may lie partly or wholly
+ *                            at negative coordinates: nothing here knows an image size, as in the reference.
+ *   dt_off     (P+1) i32
+ *   gt_bits    (pool) u8     the instances' cropped bitmaps, one byte per pixel (0 / non-zero), row-major, (y2 - y1 + 1) x
+ *                            (x2 - x1 + 1) of the instance's bound, instance r's at [gt_pix_off[r], gt_pix_off[r+1])
+ *   gt_pix_off (NG+1) i64;  gt_bound (NG,4) i32 x1, y1, x2, y2 (np.round(mask_bound).astype(int));  gt_off (P+1) i32
+ *   gt_area    (NG) i32      the bitmap's number of set pixels (the host counts it once)
+ *   iou_off    (P+1) i32     as for sn_rle_iou: iou_off[p+1] - iou_off[p] = D_p * G_p
+ * PRECONDITIONS, checked on the host and not on the device: x2 >= x1 and y2 >= y1 for every box and bound (a violated one yields
+ * counts of 0, never an access out of bounds); coordinates below 2^30 in magnitude; the offsets are consistent prefix sums; scores
+ * are finite.  An instance whose bitmap length is not its bound's area is never read and has overlap 0.
+ * sn_vocsds_mask_iou, one launch, a workgroup per detection:
+ *   dt_area (ND) i32       the pixels >= binary_thresh of the map resized to its box
+ *   iou     (n_pairs) f64  detection-major in arrival order; for instance g of the detection's problem: 0 if the intersection
+ *                          rectangle of the two integer boxes is empty; else inter = the pixels set in both inside it, union =
+ *                          dt_area + gt_area - inter, 0 if union < 1, else (double)inter / (double)union.
+ *   THE RESIZE AND THE THRESHOLD ARE THE PASTE'S -- the float32 path documented at sn_rle_paste above, the exact-2x area average
+ *   included, compared >= binary_thresh in float32 -- SPECIFIED BY THIS PROJECT AND NOT PINNED TO OPENCV (the reference calls
+ *   cv2.resize); one copy of that arithmetic serves both (csrc/paste_bit.h).  Everything else here is pinned to the reference.
+ * sn_vocsds_match_iou, one launch, a workgroup per problem.  Per detection cur = -1000.0 and the FIRST instance with ov > cur in
+ *   ascending arrival order is its candidate: an instance of overlap 0 is a candidate, a problem without instances has none.
+ *   Detections are ranked by descending score, EQUAL SCORES BY ARRIVAL ORDER (this library's rule, as sn_voc_match).  For every
+ *   threshold t: cur >= t (NOT strict, unlike sn_voc_match) and the detection is the first in rank among those claiming that
+ *   instance: tp; later claimants (already_detect): fp; cur < t or no candidate: fp.  There is no difficult flag.
+ *   dt_best (ND) i32 1 + arrival index of the candidate, 0 = none;  dt_iou (ND) f64 cur (-1000 without a candidate);
+ *   dt_tp, dt_fp (T,ND) u8;  gt_det (T,NG) i32 1 + arrival index of the detection that took the instance, 0 = none.
+ * Every element of every output is written on every call; no float atomics (integer adds and one integer min in LDS), no host
+ * read-back, the same bits every run.  max_box_pixels = the largest bw * bh, n_pairs = iou_off[P], max_*_per_problem: known to the
+ * caller from building the tables, checked against the limits.
+ * Refused before any launch, by a message that names the function and the condition: a NULL tensor; P < 1; for the overlaps ND < 1
+ * or M < 1; M above SN_VOCSDS_MAX_M (the map is staged in LDS); T outside [1, SN_VOC_MAX_T]; a problem with more than
+ * SN_VOC_MAX_DT detections or SN_VOC_MAX_GT instances; bw * bh, ND, NG or the pairs of a call at or above 2^31; T * ND or T * NG
+ * past 32 bits.  No workspace is needed.
+ * sn_vocsds_limits: h_out6 (HOST) = {MAX_DT, MAX_GT, MAX_T, MAX_M, threads per workgroup = box columns per round of
+ * sn_vocsds_mask_iou, the largest bw * bh (2^31 - 1)}. */
+#define SN_VOCSDS_MAX_M 64
+int sn_vocsds_limits(int32_t *h_out6);
+int sn_vocsds_mask_iou(const float *masks, const int32_t *dt_box, const int32_t *dt_off, const uint8_t *gt_bits,
+                       const int64_t *gt_pix_off, const int32_t *gt_bound, const int32_t *gt_area, const int32_t *gt_off,
+                       const int32_t *iou_off, int P, int M, float binary_thresh, int max_gt_per_problem, long ND, long NG,
+                       long n_pairs, long max_box_pixels, int32_t *dt_area, double *iou, sn_stream_t stream);
+int sn_vocsds_match_iou(const double *dt_score, const int32_t *dt_off, const int32_t *gt_off, const double *iou,
+                        const int32_t *iou_off, const double *iou_thrs, int P, int T, int max_dt_per_problem,
+                        int max_gt_per_problem, long ND, long NG, int32_t *dt_best, double *dt_iou, uint8_t *dt_tp, uint8_t *dt_fp,
+                        int32_t *gt_det, sn_stream_t stream);
+
 /* Proposal roidb (lib/dataset/imdb.py:81-204, 291-419): what turns an RPN proposals pickle into the roidb of the negative-chip run.
  * Ragged batches of I images through (I+1) i32 prefix offsets; all tensors are device pointers except h_out6.  PRECONDITIONS, not
  * checked on the device: rows are finite with x2 >= x1 and y2 >= y1 (so that no union is 0).

@@ -35,6 +35,7 @@ EXTRA = {
     "coco_segm.hip": ["-ffp-contract=off"],
     "mask_rle.hip": ["-ffp-contract=off"],
     "voc_eval.hip": ["-ffp-contract=off"],
+    "voc_segm.hip": ["-ffp-contract=off"],
     "prop_roidb.hip": ["-ffp-contract=off"],
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

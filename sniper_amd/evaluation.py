@@ -16,6 +16,9 @@ section 20).
 
 COCO masks (`imdb.evaluate_sds`, COCOeval with useSegm = 1) from run-length encoded masks: COCOSegmEvaluator at the end of this
 file (sn_rle_stats / sn_rle_iou / sn_coco_match_iou, sniper_amd/csrc/coco_segm.hip).
+
+PASCAL VOC masks (voc_eval_sds, the mask AP of the FCIS / DCN lineage): evaluate_sds_voc and VOCSegmEvaluator, last in this file
+(sn_vocsds_mask_iou / sn_vocsds_match_iou, sniper_amd/csrc/voc_segm.hip).
 """
 import numpy as np
 
@@ -918,3 +921,198 @@ def evaluate_sds(all_boxes, all_masks, roidb, num_classes, binary_thresh=0.4, pa
     sides: ground truth from the roidb (COCOSegmEvaluator.from_roidb), detections as lists of RLE dicts beside all_boxes ->
     COCOSegmResult; print(result.summary()) gives the reference's twelve lines"""
     return COCOSegmEvaluator.from_roidb(roidb, num_classes, params).evaluate(all_boxes, all_masks, binary_thresh=binary_thresh)
+
+
+# ---- PASCAL VOC masks ------------------------------------------------------------------------------------
+# The fourth cell of the grid (two data sets, two annotation types): the mask AP of PASCAL VOC / SBD, voc_eval_sds
+# (lib/dataset/pascal_voc_eval.py:184-272) with mask_overlap (lib/mask/mask_transform.py:40-70).  It is NOT COCOeval with other
+# parameters: the overlap is taken between the thresholded (M, M) map resized to its rounded box and the cropped instance mask in its
+# bound (no image size, no RLE, no bounding-box gate), a match needs ov >= t, only the first instance of maximal overlap is looked
+# at, an instance already detected makes the detection a false positive, there is no difficult flag, and the AP is always the
+# 11-point one.  sn_vocsds_mask_iou and sn_vocsds_match_iou (sniper_amd/csrc/voc_segm.hip, DESIGN.md section 24) do the overlaps and
+# the matching, sn_voc_accumulate the curves, unchanged.  The host rounds the boxes and builds the pools and offsets (numpy).
+__all__ += ['VOCSegmEvaluator', 'VOCSegmResult', 'evaluate_sds_voc', 'round_mask_boxes']
+
+
+def round_mask_boxes(rows, what='round_mask_boxes'):
+    """np.round(box).astype(int) of voc_eval_sds (pascal_voc_eval.py:233) for every detection row (x1, y1, x2, y2, ...), taken in
+    float64 as the reference's new_boxes holds them -> (n,4) int32.  Nothing is clipped: the reference knows no image size here.  A box
+    with x2 < x1 or y2 < y1 after the rounding is refused with a ValueError that names the detection (the reference's cv2.resize fails
+    on it too)."""
+    b = np.round(np.array(np.asarray(rows)[:, :4], np.float64).reshape(-1, 4))
+    if len(b) and np.abs(b).max() >= 2 ** 30:
+        raise ValueError('%s: detection %d has a coordinate of magnitude 2^30 or more' % (what, int(np.argmax(np.abs(b).max(axis=1)))))
+    b = b.astype(np.int32)
+    bad = np.flatnonzero((b[:, 2] < b[:, 0]) | (b[:, 3] < b[:, 1]))
+    if len(bad):
+        raise ValueError('%s: detection %d has the box %s after rounding: x2 < x1 or y2 < y1' % (what, bad[0], b[bad[0]].tolist()))
+    return b
+
+
+class VOCSegmResult(VOCBoxResult):
+    """VOCBoxResult of a mask evaluation: ap07 (what voc_eval_sds returns), ap_area (T,K), ap = ap07, mean_ap (T,), npos (K,),
+    summary() (the box evaluation's lines; voc_eval_sds always takes the 11-point metric), timing per stage"""
+
+    def __init__(self, ap07, ap_area, npos, class_names, thresholds, timing=None):
+        VOCBoxResult.__init__(self, ap07, ap_area, npos, class_names, True, thresholds, timing)
+
+
+class VOCSegmEvaluator(object):
+    """records[i]: the list parse_inst (pascal_voc_eval.py:275-318) returns for image i -- dicts with `mask` (bool (h, w), the
+    instance cropped to its bound), `mask_bound` (x1, y1, x2, y2; rounded here as the reference rounds it, np.round(...).astype(int))
+    and `mask_cls` (1 .. K, the index into the class list with the background at 0).  class_names: the K foreground classes (a
+    leading '__background__' is dropped).  A mask whose shape is not its bound's is refused with a ValueError."""
+
+    def __init__(self, records, num_images, class_names, thresholds=(0.5, 0.7)):
+        names = list(class_names)
+        self.class_names = names[1:] if names and names[0] == '__background__' else names
+        self.num_images = int(num_images)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        assert len(records) == self.num_images, '%d records for %d images' % (len(records), self.num_images)
+        K = len(self.class_names)
+        img, cat, bound, bits, area = [], [], [], [], []
+        for i, rec in enumerate(records):
+            for j, inst in enumerate(rec):
+                b = np.round(np.asarray(inst['mask_bound'], np.float64).reshape(4)).astype(np.int64)
+                m = np.asarray(inst['mask'])
+                c = int(inst['mask_cls'])
+                if m.ndim != 2 or m.shape != (b[3] - b[1] + 1, b[2] - b[0] + 1):
+                    raise ValueError('VOCSegmEvaluator: instance %d of image %d has a mask of shape %s in the bound %s' % (j, i, m.shape, b.tolist()))
+                if not 1 <= c <= K:
+                    raise ValueError('VOCSegmEvaluator: instance %d of image %d has mask_cls %d, outside 1 .. %d' % (j, i, c, K))
+                if np.abs(b).max() >= 2 ** 30:
+                    raise ValueError('VOCSegmEvaluator: instance %d of image %d has a coordinate of magnitude 2^30 or more' % (j, i))
+                m = (m != 0).astype(np.uint8).reshape(-1)
+                img.append(i); cat.append(c - 1); bound.append(b); bits.append(m); area.append(int(m.sum()))
+        n = len(img)
+        self.gt = {'image': np.array(img, np.int64).reshape(n), 'category': np.array(cat, np.int64).reshape(n),
+                   'bound': np.array(bound, np.int32).reshape(n, 4), 'area': np.array(area, np.int32).reshape(n), 'bits': bits}
+
+    def _pool(self, order):
+        """the instances' bitmaps in CSR order -> (bits (pool,) uint8, pix_off (NG+1) int64)"""
+        parts = [self.gt['bits'][g] for g in order]
+        off = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([len(p) for p in parts], out=off[1:])
+        return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), off
+
+    def convert_detections(self, all_boxes, all_masks):
+        """-> (boxes (ND,4) int32 rounded, scores (ND,) float64, masks (ND,M,M) float32, (K, I) row counts), class-major, image, row.
+        A box that rounds to x2 < x1 or y2 < y1 is a ValueError naming its class, image and row."""
+        K, I = len(self.class_names), self.num_images
+        counts = _cell_counts(all_boxes, K, I)
+        assert len(all_masks) == K + 1, 'all_masks[class][image]: %d classes (with the background) for %d categories' % (len(all_masks), K)
+        host = lambda d: np.asarray(d.cpu() if hasattr(d, 'cpu') else d)
+        cells, rows, maps, M = [], [], [], None
+        for k in range(K):
+            assert len(all_masks[k + 1]) == I, 'all_masks[%d] has %d images, the ground truth %d' % (k + 1, len(all_masks[k + 1]), I)
+            for i in np.flatnonzero(counts[k]):
+                r, m = host(all_boxes[k + 1][i]).reshape(-1, 5), host(all_masks[k + 1][i])
+                if m.ndim != 3 or m.shape[0] != len(r) or m.shape[1] != m.shape[2] or (M is not None and m.shape[1] != M):
+                    raise ValueError('VOCSegmEvaluator: all_masks[%d][%d] has the shape %s for %d boxes%s' % (
+                        k + 1, i, m.shape, len(r), '' if M is None else ' and M = %d' % M))
+                M = m.shape[1]
+                cells.append((k + 1, i))
+                rows.append(r.astype(np.float64))          # exact: the reference's new_boxes is a float64 array too
+                maps.append(m)
+        if not rows:
+            return np.zeros((0, 4), np.int32), np.zeros(0, np.float64), np.zeros((0, 1, 1), np.float32), counts
+        raw = np.concatenate(rows, axis=0)
+        try:
+            boxes = round_mask_boxes(raw)
+        except ValueError:                                 # name the cell and the row within it
+            for (c, i), r in zip(cells, rows):
+                try:
+                    round_mask_boxes(r)
+                except ValueError as e:
+                    raise ValueError('VOCSegmEvaluator: class %d, image %d: %s' % (c, i, e))
+            raise
+        masks = np.ascontiguousarray(np.concatenate(maps, axis=0), np.float32)
+        return boxes, np.ascontiguousarray(raw[:, 4]), masks, counts
+
+    def evaluate(self, all_boxes, all_masks, binary_thresh=0.4, return_matches=False):
+        """all_boxes[class][image] = (n,5) rows x1, y1, x2, y2, score and all_masks[class][image] = (n,M,M) probabilities as
+        mask_inference.predict_masks returns them (class 0 = background) -> VOCSegmResult.  return_matches adds result.matches: the
+        offsets, the rounded boxes, dt_area, iou / iou_off, the outputs of sn_vocsds_match_iou, order, rec, prec and cls_off."""
+        import torch
+        from . import hip
+        dev = hip.require_gpu()
+        thrs = np.asarray(self.thresholds, np.float64)
+        T, K = len(thrs), len(self.class_names)
+        t0 = _now(torch)
+        boxes, scores, masks, counts = self.convert_detections(all_boxes, all_masks)
+        ND, NG, M = len(boxes), len(self.gt['image']), masks.shape[1]
+        pr = _problem_offsets(counts, self.gt['category'], self.gt['image'])
+        P = pr['P']
+        if P == 0:                                    # neither detections nor instances: every AP is 0, as the reference's
+            return VOCSegmResult(np.zeros((T, K)), np.zeros((T, K)), np.zeros(K, np.int32), self.class_names, self.thresholds)
+        o = pr['gt_order']
+        bits, pix_off = self._pool(o)
+        gcount = np.diff(pr['gt_off'].astype(np.int64))
+        iou_off64 = np.concatenate([[0], np.cumsum(pr['dt_counts'].astype(np.int64) * gcount)])
+        if iou_off64[-1] >= 2 ** 31:
+            raise ValueError('VOCSegmEvaluator: %d (detection, instance) pairs in one call, 2^31 at the most' % iou_off64[-1])
+        n_pairs = int(iou_off64[-1])
+        pixels = (boxes[:, 2].astype(np.int64) - boxes[:, 0] + 1) * (boxes[:, 3].astype(np.int64) - boxes[:, 1] + 1)
+        if ND and pixels.max() >= 2 ** 31:
+            raise ValueError('VOCSegmEvaluator: detection %d has a box of %d pixels, below 2^31 required' % (int(np.argmax(pixels)), pixels.max()))
+        cls_off = pr['dt_off'][pr['cat_off']]
+        per_class = np.diff(cls_off.astype(np.int64))
+        ap07_thrs = np.arange(0., 1.1, 0.1)
+        t1 = _now(torch)
+        some = lambda a, dtype: hip.dev(a) if len(a) else torch.zeros((4,), dtype=dtype, device=dev)
+        d_score = some(scores, torch.float64)
+        d_bits, d_pix, d_bound = some(bits, torch.uint8), hip.dev(pix_off), some(self.gt['bound'][o], torch.int32)
+        d_area, d_zero = some(self.gt['area'][o], torch.int32), torch.zeros((max(NG, 1),), dtype=torch.uint8, device=dev)
+        d_dt_off, d_gt_off, d_cat_off = hip.dev(pr['dt_off']), hip.dev(pr['gt_off']), hip.dev(pr['cat_off'])
+        d_iou_off, d_thr = hip.dev(iou_off64.astype(np.int32)), hip.dev(thrs)
+        empty = lambda dtype, *shape: torch.empty([max(int(np.prod(shape)), 1)], dtype=dtype, device=dev)
+        dt_area, iou = empty(torch.int32, ND), empty(torch.float64, n_pairs)
+        dt_best, dt_iou = empty(torch.int32, ND), empty(torch.float64, ND)
+        dt_tp, dt_fp, gt_det = empty(torch.uint8, T, ND), empty(torch.uint8, T, ND), empty(torch.int32, T, NG)
+        order, rec, prec = empty(torch.int32, ND), empty(torch.float64, T, ND), empty(torch.float64, T, ND)
+        npos = torch.empty((K,), dtype=torch.int32, device=dev)
+        ap07 = torch.empty((T, K), dtype=torch.float64, device=dev)
+        ap_area = torch.empty((T, K), dtype=torch.float64, device=dev)
+        ws = torch.empty(int(hip.query('sn_voc_accumulate_workspace_bytes', ND, T)), dtype=torch.uint8, device=dev)
+        if ND:
+            d_masks, d_box = hip.dev(masks), hip.dev(boxes)
+        t2 = _now(torch)
+        if ND:                                        # without detections there is no overlap to take
+            hip.call('sn_vocsds_mask_iou', d_masks, d_box, d_dt_off, d_bits, d_pix, d_bound, d_area, d_gt_off, d_iou_off, P, M,
+                     float(np.float32(binary_thresh)), pr['max_gt'], ND, NG, n_pairs, int(pixels.max()), dt_area, iou, hip.stream())
+        ti = _now(torch)
+        hip.call('sn_vocsds_match_iou', d_score, d_dt_off, d_gt_off, iou, d_iou_off, d_thr, P, T, pr['max_dt'], pr['max_gt'], ND, NG,
+                 dt_best, dt_iou, dt_tp, dt_fp, gt_det, hip.stream())
+        tm = _now(torch)
+        hip.call('sn_voc_accumulate', d_score, d_dt_off, d_gt_off, d_cat_off, d_zero, dt_tp, dt_fp, ap07_thrs, P, K, T,
+                 int(per_class.max()), ND, NG, ws, ws.numel(), order, rec, prec, npos, ap07, ap_area, hip.stream())
+        t3 = _now(torch)
+        h_ap07, h_area, h_npos = ap07.cpu().numpy(), ap_area.cpu().numpy(), npos.cpu().numpy()
+        matches = None
+        if return_matches:
+            rd = lambda x, *shape: x[:int(np.prod(shape))].reshape(shape).cpu().numpy()
+            matches = dict(pr, cls_off=cls_off, dt_box=boxes, dt_score=scores, iou_off=iou_off64.astype(np.int32), dt_area=rd(dt_area, ND),
+                           iou=rd(iou, n_pairs), dt_best=rd(dt_best, ND), dt_iou=rd(dt_iou, ND), dt_tp=rd(dt_tp, T, ND),
+                           dt_fp=rd(dt_fp, T, ND), gt_det=rd(gt_det, T, NG), order=rd(order, ND), rec=rd(rec, T, ND), prec=rd(prec, T, ND))
+        t4 = _now(torch)
+        # seconds: host = rounding, pools and CSR offsets; upload = allocations + copies to the device; mask_iou, match, accumulate =
+        # the three entry points; download = the APs and npos (and the matches, if asked for)
+        res = VOCSegmResult(h_ap07, h_area, h_npos, self.class_names, self.thresholds,
+                            {'host_s': t1 - t0, 'upload_s': t2 - t1, 'kernels_s': t3 - t2, 'mask_iou_s': ti - t2, 'match_s': tm - ti,
+                             'accumulate_s': t3 - tm, 'download_s': t4 - t3, 'problems': P, 'detections': ND, 'instances': NG,
+                             'pairs': n_pairs})
+        if matches is not None:
+            res.matches = matches
+        return res
+
+
+def evaluate_sds_voc(all_boxes, all_masks, records, num_classes, class_names=None, binary_thresh=0.4):
+    """The mask AP of a PASCAL VOC / SBD test run in one call: voc_eval_sds per class at 0.5 and 0.7.  records[i] = parse_inst's list
+    for image i, detections and masks as Tester.aggregate and mask_inference.predict_masks return them -> VOCSegmResult;
+    print(result.summary()) gives the AP lines"""
+    if class_names is None:
+        class_names = VOC_CLASSES if num_classes == len(VOC_CLASSES) + 1 else ['class%d' % c for c in range(1, num_classes)]
+    names = list(class_names)
+    names = names[1:] if names and names[0] == '__background__' else names
+    assert len(names) == num_classes - 1, '%d class names for %d classes with the background' % (len(names), num_classes)
+    return VOCSegmEvaluator(records, len(records), names).evaluate(all_boxes, all_masks, binary_thresh=binary_thresh)

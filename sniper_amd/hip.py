@@ -61,6 +61,13 @@ def query(name, *args):
     return lib().raw(name)(*[_conv(a) for a in args])
 
 
+def vocsds_limits():
+    """sn_vocsds_limits (include/sniper_hip.h) -> dict: the caps of the PASCAL VOC mask evaluation; needs no device"""
+    out = (ctypes.c_int32 * 6)()
+    lib().call('sn_vocsds_limits', out)
+    return dict(zip(('max_dt', 'max_gt', 'max_t', 'max_m', 'threads', 'max_box_pixels'), (int(v) for v in out)))
+
+
 class WgradDesc(ctypes.Structure):
     """sn_wgrad_desc (include/sniper_hip.h): one layer of a batched weight-gradient launch."""
     _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p)] + \
