@@ -597,6 +597,39 @@ int sn_coco_match_iou(const double *dt, const int32_t *dt_off, const int32_t *kp
                       int32_t *dt_rank, int32_t *dt_match, uint8_t *dt_ignore, int32_t *gt_match, uint8_t *gt_ignore,
                       sn_stream_t stream);
 
+/* Compressed string counts: rleToString / rleFrString (maskApi.c:181-208), the `counts` of a results file.  Six bits per character
+ * from chr(48): five of payload, 0x20 = another character of this count follows, 0x10 of a count's last character = its sign; from
+ * the fourth count on the value coded is the difference to the count two before.  Integer arithmetic, exact bytes.
+ * Masks are pooled as everywhere here: cnts (total_runs) u32 behind run_off (N+1) i32, characters (total_chars) u8 behind str_off
+ * (N+1) i32, no terminator stored.  Each direction is two calls with a host scan between them: lengths, then the fill at the offsets
+ * the caller built from them.  The offsets are given TWICE, on the device (what the kernels read) and as the HOST array they were
+ * uploaded from (h_*, what the entry point checks before it launches).  One workgroup of one wave per mask, chunks of 64 counts /
+ * characters with a carry; plain vector stores, no atomics, no workspace, one fixed order.
+ * Encoding, count i of a mask: x = cnts[i] - (i > 2 ? cnts[i-2] : 0) in int64 takes the smallest k >= 1 with -2^(5k-1) <= x < 2^(5k-1)
+ *   characters; character j is (((x >> 5j) & 0x1f) | (j < k-1 ? 0x20 : 0)) + 48.  k <= 7 for every pair of uint32 counts (the
+ *   reference allocates six per count and is undefined where |x| >= 2^29).
+ *   sn_rle_string_len: str_len (N) i32 = the bytes of every mask's string.  sn_rle_to_string: chars, mask n at str_off[n]; nothing is
+ *   written outside [str_off[n], str_off[n+1]).
+ * Decoding, modulo 2^32: payloads OR-ed at 5j, sign extension where the last character carries 0x10, then cnts[i] = x_i + cnts[i-2]
+ *   for i > 2 -- two interleaved prefix sums, scanned.
+ *   sn_rle_string_count: m (N) i32 = the counts of every string (its characters without 0x20), status (N) i32 = 0 ok | 1 the string
+ *   ends inside a count | 2 a character outside chr(48) .. chr(111) | 3 a count of more than 7 characters; where several hold, 2
+ *   comes before 1 before 3 (a foreign character makes the other bits meaningless).  sn_rle_from_string: cnts, string n at
+ *   run_off[n]; a string whose status is not 0 writes nothing, and nothing is written outside [run_off[n], run_off[n+1]).
+ * sn_rle_string_limits: h_out3 (HOST) = {threads per workgroup, counts / characters per chunk, the most characters of a count (7)}.
+ * Refused before any launch: NULL operands; N < 1; offsets that do not start at 0, that decrease, or that do not end at the total
+ * given; totals past 32-bit indexing. */
+int sn_rle_string_limits(int32_t *h_out3);
+int sn_rle_string_len(const uint32_t *cnts, const int32_t *run_off, const int32_t *h_run_off, long N, long total_runs, int32_t *str_len,
+                      sn_stream_t stream);
+int sn_rle_to_string(const uint32_t *cnts, const int32_t *run_off, const int32_t *h_run_off, const int32_t *str_off,
+                     const int32_t *h_str_off, long N, long total_runs, long total_chars, uint8_t *chars, sn_stream_t stream);
+int sn_rle_string_count(const uint8_t *chars, const int32_t *str_off, const int32_t *h_str_off, long N, long total_chars, int32_t *m,
+                        int32_t *status, sn_stream_t stream);
+int sn_rle_from_string(const uint8_t *chars, const int32_t *str_off, const int32_t *h_str_off, const int32_t *run_off,
+                       const int32_t *h_run_off, const int32_t *status, long N, long total_chars, long total_runs, uint32_t *cnts,
+                       sn_stream_t stream);
+
 /* PASCAL VOC box evaluation (lib/dataset/pascal_voc_eval.py:116-181 voc_eval, :39-70 voc_ap).  float64 and integer counts
  * throughout: `rec`, `prec` and `ap07` are the reference's bits, `ap_area` is its sum in another order (each term >= 0, every partial
  * sum <= 1: within (n - 1) * 2^-53 of the exact sum for n recall changes).  A PROBLEM is one (class, image) pair with at least one
