@@ -883,6 +883,42 @@ int sn_weight_transpose(const float *w_oti, void *wt_ito_f16, int O, int T, int 
  * total_tiles = the final sum. */
 int sn_weight_transpose_batched(const void *desc, int n_desc, int total_tiles, sn_stream_t stream);
 
+/* Detections drawn into images (lib/data_utils/visualization.py:21-57 draws with matplotlib -- the raster here
+ * is THIS PROJECT'S, in integer arithmetic, stated in full in that section and restated in numpy by tests/render_ref.py).  One launch
+ * renders a batch of I images: tiles x images, no atomics, no workspace, no host read-back, the same bits every run.
+ *   form    SN_RENDER_UINT8: src is uint8 HWC RGB, image i at byte 3 * pix_off[i], hw[i] = (h, w) rows of 3 * w bytes.
+ *           SN_RENDER_TENSOR: src is float32, image i at element 3 * pix_off[i] as three planes of h * w (a (B, 3, Hm, Wm) network
+ *           input has pix_off[i] = i * Hm * Wm); channel j of a pixel is x + mean_j in float32, truncated toward zero and CLAMPED to
+ *           0 .. 255 (numpy's astype(uint8) of the reference wraps instead).
+ *   hw (I,2) i32, pix_off (I+1) i64 in pixels, out uint8 HWC RGB with the same offsets; max_h / max_w: the largest h and w (they
+ *   size the grid); total_pixels = pix_off[I].
+ *   Items of image i: item_off[i] .. item_off[i+1] (at most SN_RENDER_MAX_ITEMS = max_items of the largest image), each with
+ *     rects (n,4) i32 x1, y1, x2, y2 inclusive, anywhere (coordinates are clamped to +-2^29); colors (n,3) u8 RGB;
+ *     mask_idx (n) i32: a row of masks (n_masks, M, M) f32 or -1 -- the mask is pasted into rect by the arithmetic of sn_rle_paste
+ *     with binary_thresh, so rect must then be that paste's box (0 <= x1 <= x2 < w, likewise y: the caller's precondition);
+ *     text_off (n+1) i32 into text (total_text) i32, glyph indices into atlas (G, gh, gw) u8 coverage.  h_text: the same indices in
+ *     HOST memory or NULL -- given, every index outside [0, G) is refused; not given, that is the caller's precondition (the kernel
+ *     skips such a glyph, it never reads outside the atlas).
+ *   Layers per pixel: source; mask fill p = (p * (256 - mask_alpha) + c * mask_alpha + 128) >> 8; outline (inside rect, not inside rect
+ *   shrunk by line_width; opaque, later items over earlier); label (a box of len * gw + 2 by gh + 2 at x1, above rect when its top
+ *   y1 - (gh + 2) >= 0 and at y1 + line_width otherwise: the blend with 128, then glyph pixels toward white by cov + (cov >> 7)).
+ * Refused before any launch, by a message that names the function and the condition: a NULL tensor where one is needed (masks only
+ * when n_masks > 0, text and atlas only when total_text > 0, the item tables only when total_items > 0); an unknown form; I outside
+ * 1 .. 65535; max_items above SN_RENDER_MAX_ITEMS; M outside 1 .. 1024; mask_alpha outside 0 .. 256; line_width outside 1 .. 65536; an
+ * atlas cell outside 1 .. 256 per side; a glyph index of h_text outside [0, G); sizes past 32-bit indexing.
+ * sn_render_limits: h_out5 (HOST) = {SN_RENDER_MAX_ITEMS, tile width, tile height, items per culling round (the LDS list), threads
+ * per workgroup}. */
+#define SN_RENDER_MAX_ITEMS 4096
+#define SN_RENDER_UINT8 0
+#define SN_RENDER_TENSOR 1
+int sn_render_limits(int32_t *h_out5);
+int sn_render_dets(int form, const void *src, const int32_t *hw, const int64_t *pix_off, int I, int max_h, int max_w,
+                   long total_pixels, const int32_t *item_off, int max_items, long total_items, const int32_t *rects,
+                   const uint8_t *colors, const int32_t *mask_idx, const int32_t *text_off, const int32_t *text,
+                   const int32_t *h_text, long total_text, const uint8_t *atlas, int G, int gh, int gw, const float *masks,
+                   int n_masks, int M, float binary_thresh, int mask_alpha, int line_width, float mean0, float mean1, float mean2,
+                   uint8_t *out, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

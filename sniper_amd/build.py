@@ -37,6 +37,7 @@ EXTRA = {
     "voc_eval.hip": ["-ffp-contract=off"],
     "voc_segm.hip": ["-ffp-contract=off"],
     "prop_roidb.hip": ["-ffp-contract=off"],
+    "render.hip": ["-ffp-contract=off"],
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

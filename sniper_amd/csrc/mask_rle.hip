@@ -284,21 +284,8 @@ __global__ __launch_bounds__(kThreads) void poly_union_kernel(const int32_t *__r
 
 // ---- the paste of mask probabilities (lib/mask/mask_voc2coco.py:39-49) -----------------------------------------------------
 // Detection n: an (M, M) float32 mask resized to its box (bw = x2 - x1 + 1, bh = y2 - y1 + 1), thresholded, zeros outside the box, the
-// whole (h, w) image run-length encoded column-major.  The resize and the threshold -- PasteBox, paste_bit -- live in paste_bit.h,
-// shared with the region overlap of voc_segm.hip.
-__device__ __forceinline__ PasteBox paste_box(const int32_t *__restrict__ boxes, const int32_t *__restrict__ hw, int n, int M) {
-  PasteBox b;
-  b.x1 = boxes[4 * n];
-  b.y1 = boxes[4 * n + 1];
-  b.bw = boxes[4 * n + 2] - b.x1 + 1;
-  b.bh = boxes[4 * n + 3] - b.y1 + 1;
-  b.h = hw[2 * n];
-  b.w = hw[2 * n + 1];
-  b.sx = 1. / ((double)b.bw / M);
-  b.sy = 1. / ((double)b.bh / M);
-  b.area = 2 * b.bw == M && 2 * b.bh == M;
-  return b;
-}
+// whole (h, w) image run-length encoded column-major.  The resize and the threshold -- PasteBox, paste_box, paste_bit -- live in
+// paste_bit.h, shared with the region overlap of voc_segm.hip and the mask overlay of render.hip.
 // the value changes of box column c in column-major order: calls emit(position) for each, in ascending order.  A box of full image
 // height is contiguous from one column to the next; otherwise a column starts after zeros and a set last bit is closed behind it
 // (unless the image ends there).

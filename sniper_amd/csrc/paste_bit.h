@@ -1,6 +1,6 @@
 // paste_bit.h -- the ONE copy of the resize-and-threshold arithmetic of a mask probability map in its box: included by mask_rle.hip
-// (the paste of mask_voc2coco into an image, sn_rle_paste) and by voc_segm.hip (the region overlap of voc_eval_sds, sn_vocsds_mask_iou).
-// Both must be compiled with -ffp-contract=off (sniper_amd/build.py): the two passes round every product and sum on their own.
+// (the paste of mask_voc2coco into an image, sn_rle_paste), by voc_segm.hip (the region overlap of voc_eval_sds, sn_vocsds_mask_iou)
+// and by render.hip (the mask overlay of sn_render_dets).  All must be compiled with -ffp-contract=off (sniper_amd/build.py): the two passes round every product and sum on their own.
 //
 // Detection n: an (M, M) float32 mask resized to its box (bw = x2 - x1 + 1, bh = y2 - y1 + 1) and thresholded.  The resize is THIS
 // PROJECT'S statement of the float32 INTER_LINEAR path of the algorithm oracle/cv_resize.py documents for uint8 (not pinned to OpenCV):
@@ -17,6 +17,20 @@ struct PasteBox {
   double sx, sy;
   bool area;
 };
+// detection n of a call: its box (x1, y1, x2, y2) inclusive, its image's (h, w)
+__device__ __forceinline__ PasteBox paste_box(const int32_t *__restrict__ boxes, const int32_t *__restrict__ hw, int n, int M) {
+  PasteBox b;
+  b.x1 = boxes[4 * n];
+  b.y1 = boxes[4 * n + 1];
+  b.bw = boxes[4 * n + 2] - b.x1 + 1;
+  b.bh = boxes[4 * n + 3] - b.y1 + 1;
+  b.h = hw[2 * n];
+  b.w = hw[2 * n + 1];
+  b.sx = 1. / ((double)b.bw / M);
+  b.sy = 1. / ((double)b.bh / M);
+  b.area = 2 * b.bw == M && 2 * b.bh == M;
+  return b;
+}
 // the mask bit of column c, row r of the box; S may be global or LDS memory, M * M floats
 __device__ __forceinline__ bool paste_bit(const float *__restrict__ S, int M, const PasteBox &b, int c, int r, float thr) {
   float v;

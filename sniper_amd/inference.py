@@ -481,10 +481,40 @@ class Tester(object):
                   vis_ext='.png'):
         n_scales = len(scale_cls_dets)
         assert n_scales == len(self.cfg.TEST.VALID_RANGES), 'A valid range should be specified for each test scale'
-        if not vis:
-            done = self.aggregate_device(scale_cls_dets)
-            if done is not None:
-                return done
+        all_boxes = self.aggregate_device(scale_cls_dets)
+        if all_boxes is None:
+            all_boxes = self._aggregate_host(scale_cls_dets)
+        if vis:
+            # the final boxes drawn into their images on the device (sniper_amd/visualization.py), one file per image; the
+            # reference hard-codes '.pdf' here (:219-220), vis_ext is honoured instead
+            from .visualization import render_results
+            render_results(self.roidb, all_boxes, self.class_names, self._vis_dir(vis_path, cache_name),
+                           threshold=0.5, vis_ext=vis_ext, names=[vis_name] * self.num_images if vis_name else None)
+        return all_boxes
+
+    def _vis_dir(self, vis_path, cache_name):
+        return vis_path or os.path.join(getattr(self.cfg.TEST, 'VISUALIZATION_PATH', os.path.join('debug', 'visualization')), cache_name)
+
+    def _vis_names(self):
+        return list(self.class_names) if self.class_names is not None else \
+            ['__background__'] + ['class %d' % j for j in range(1, self.num_classes)]
+
+    def _vis_chips(self, data, dets_of, file_of, class_names, out_dir, vis_ext):
+        """The chips of one batch drawn from its `data` tensor while it is still in HBM, one device call (visualization.render_batch):
+        dets_of(i) = the per-class rows of chip i, scale im_info[i, 2], the reference's transform_im means (:24)."""
+        from .visualization import _save, render_batch
+        if not os.path.isdir(out_dir):
+            os.makedirs(out_dir)
+        x = data['data']
+        x = x._data if hasattr(x, '_data') else x.asnumpy()           # (a device tensor, or the numpy array of a cpu context)
+        im_info = data['im_info'].asnumpy()
+        B = int(x.shape[0])
+        pics = render_batch(x.float() if isinstance(x, torch.Tensor) else np.asarray(x, np.float32), [dets_of(i) for i in range(B)], class_names, [float(im_info[i, 2]) for i in range(B)],
+                            np.asarray(self.cfg.network.PIXEL_MEANS, np.float32)[[2, 1, 0]], 0.5)
+        for i, pic in enumerate(pics):
+            _save(pic.cpu().numpy() if isinstance(pic, torch.Tensor) else pic, os.path.join(out_dir, file_of(i) + vis_ext))
+
+    def _aggregate_host(self, scale_cls_dets):
         all_boxes = [[[] for _ in range(self.num_images)] for _ in range(self.num_classes)]
         # one batched launch instead of Pool(32).map; the problems go up as the one stacked array they are built as
         rows, sizes = aggregate_problems(scale_cls_dets, self.cfg.TEST.VALID_RANGES, self.num_images, self.num_classes, stacked=True)
@@ -608,6 +638,7 @@ class Tester(object):
         all_boxes = _Detections([[[] for _ in range(n_chips[i])] for i in range(self.num_images)] for _ in range(self.num_classes))
         all_maps = [[[] for _ in range(n_chips[i])] for i in range(self.num_images)]
         nc = self.num_classes - 1
+        nms = evaluate or vis        # `vis` implies the per-chip NMS: the reference's `evaluate or vis` (:300-312)
 
         def post(scores, boxes, data, im_ids, maps, chip_ids):
             todo = []
@@ -631,17 +662,17 @@ class Tester(object):
                 # all classes at once: rows grouped by class, RoIs ascending inside a class (= np.where per class, :290-295)
                 per_class = threshold_detections(scores[i], cboxes, cls_thresh, self.num_classes)
                 for j in range(1, self.num_classes):
-                    if evaluate:
+                    if nms:
                         todo.append((j, im_id, chip_id, per_class[j - 1]))
                     else:
                         all_boxes[j][im_id][chip_id] = per_class[j - 1]
             if scores is None:
                 return
-            if evaluate:
+            if nms:
                 final = self.nms_worker.worker_many([t[3] for t in todo])
                 for (j, im_id, chip_id, _), d in zip(todo, final):
                     all_boxes[j][im_id][chip_id] = d
-                if self.cfg.TEST.MAX_PER_IMAGE:
+                if evaluate and self.cfg.TEST.MAX_PER_IMAGE:
                     for im_id, chip_id in set((t[1], t[2]) for t in todo):
                         image_scores = np.hstack([all_boxes[j][im_id][chip_id][:, -1] for j in range(1, self.num_classes)])
                         if len(image_scores) > self.cfg.TEST.MAX_PER_IMAGE:
@@ -649,6 +680,10 @@ class Tester(object):
                             for j in range(1, self.num_classes):
                                 keep = np.where(all_boxes[j][im_id][chip_id][:, -1] >= image_thresh)[0]
                                 all_boxes[j][im_id][chip_id] = all_boxes[j][im_id][chip_id][keep, :]
+            if vis:            # the chips as the network saw them, before the boxes go back to image coordinates (:323-331); the
+                               # reference's file names carry the wall clock, these do not
+                self._vis_chips(data, lambda i: [[]] + [all_boxes[j][im_ids[i]][chip_ids[i]] for j in range(1, self.num_classes)],
+                                lambda i: '{}_{}'.format(im_ids[i], chip_ids[i]), self._vis_names(), self._vis_dir(vis_path, cache_name), vis_ext)
             if do_pruning:     # project the boxes back to image coordinates, drop those cut by a chip border (:336-353)
                 for im_id, chip_id in set(zip(im_ids.tolist(), chip_ids.tolist())):
                     crop = self.roidb[im_id]['inference_crops'][chip_id]
@@ -659,7 +694,7 @@ class Tester(object):
         # Without the per-chip NMS of `evaluate` the threshold and the pruning are one predicate per (RoI, class): the GPU applies
         # it and compacts the rows (sn_det_compact).  Batch k runs on lane k % lanes; a lane's previous batch is collected (in
         # batch order) before the lane is reused, so `lanes` forwards are in flight while the host slices an earlier batch.
-        compact = None if (evaluate or not self.device_compact) else (cls_thresh, do_pruning)
+        compact = None if (nms or not self.device_compact) else (cls_thresh, do_pruning)
         lanes = len(self.modules)
         # one lane (the default): still two batches in flight -- batch k + 1 is enqueued BEFORE batch k is collected, so the host
         # slices k under the forward of k + 1 (a lane's pinned result sets alternate: k is out of its set before k + 2 is launched)
@@ -681,8 +716,13 @@ class Tester(object):
             im_info = batch.data[1].asnumpy()
             scales = im_info[:, 2].reshape(-1, self.batch_size)
             scores, boxes, data, im_ids = self.get_proposals(batch, scales)
+            kept = []
             for cscores, cboxes, im_id in zip(scores, boxes, im_ids):
                 all_boxes[im_id] = np.hstack((cboxes[0:n_proposals, 0:4], cscores[0:n_proposals].reshape(-1, 1))).astype(np.float32)
+                kept.append(all_boxes[im_id])
+            if vis:                # the kept proposals as one class on the batch's `data` tensor (:393-400)
+                self._vis_chips(data, lambda i: [[], kept[i]], lambda i: '{}'.format(im_ids[i]), ['__background__', 'object'],
+                                self._vis_dir(None, cache_name), vis_ext)
         return all_boxes
 
 
