@@ -875,6 +875,34 @@ int sn_sgd_mom_update(float *w32, const float *grad, float *mom, void *w16, long
  * lr = d_hyper[0]*lr_mult, wd = d_hyper[1]*wd_mult. */
 int sn_sgd_mom_update_dev(float *w32, const float *grad, float *mom, void *w16, long n, const float *d_hyper, float lr_mult,
                           float wd_mult, sn_stream_t stream);
+/* The gradient guard of the optimizer pass: skip a step whose gradients hold inf / NaN, clip by global norm, report the norm -- on the
+ * device, inside the captured optimizer graph, no host synchronisation.
+ * sn_grad_guard: one pass over d_grad (n fp32, 4-byte aligned; peeled to a 16-byte boundary, then 16-byte loads) and a single-block
+ *   finalize launch.  An element g is non-finite iff !(fabsf(g) <= FLT_MAX): counted and left out of the sum; finite elements add
+ *   (double)g * (double)g (exact) to fp64 sums per thread, wave, block; one partial per block goes to d_ws
+ *   (sn_grad_guard_workspace_bytes(n, max_blocks) bytes, 8-byte aligned) and the finalize adds the partials in index order.  No
+ *   atomics: for a given (n, max_blocks, alignment of d_grad) the same bits every run.  max_blocks: 0 = the library's grid, a fixed
+ *   function of n; > 0 caps the grid (<= 65535).  d_hyper: the four floats of sn_sgd_mom_update_dev; d_hyper[3] = rescale_grad is read.
+ *   d_state, eight doubles (8-byte aligned; the caller zeroes them ONCE, [4..6] are read-modify-write by the finalize block only):
+ *     [0] norm   = sqrt(sumsq) * fabs((double)d_hyper[3]): the norm of rescale_grad * grad over the finite elements
+ *     [1] coef   = clip_global_norm > 0 ? min(1, clip_global_norm / (norm + 1e-6)) : 1   (torch.nn.utils.clip_grad_norm_; fp64)
+ *     [2] skip   = skip_nonfinite && nonfinite > 0   (0 or 1)
+ *     [3] non-finite elements of this step      [4] steps seen (+1)      [5] steps skipped (+skip)
+ *     [6] consecutive skipped steps (skip ? old + 1 : 0)                 [7] sumsq
+ * sn_grad_guard_limits: h_out4 (HOST) = {threads per block, floats per thread per trip, the default grid cap, doubles of state}.
+ * sn_sgd_mom_update_guarded_dev: sn_sgd_mom_update_dev behind that state (same head / four-wide body / tail split).  Every thread
+ *   reads coef (rounded to float) and skip once.  skip: w32, mom and w16 are NOT WRITTEN.  coef == 1 and clip_gradient <= 0: the
+ *   statement of sn_sgd_mom_update_dev, bit-identical results.  Else u = rescale * (coef * grad[i]); with clip_gradient > 0
+ *   u = clamp(u, -clip_gradient, +clip_gradient) (mx 'sgd': rescale_grad * grad is clipped, before weight decay); g = u + wd * w;
+ *   m = momentum * mom - lr * g; w += m; w16 = half(w).
+ * Refused before any launch: null pointers, n < 0, a negative or NaN clip_global_norm, a NaN clip_gradient, max_blocks outside
+ * 0 .. 65535, misaligned d_grad / d_ws / d_state. */
+int sn_grad_guard_limits(int32_t *h_out4);
+size_t sn_grad_guard_workspace_bytes(long n, int max_blocks);
+int sn_grad_guard(const float *d_grad, long n, const float *d_hyper, float clip_global_norm, int skip_nonfinite, int max_blocks,
+                  void *d_ws, double *d_state, sn_stream_t stream);
+int sn_sgd_mom_update_guarded_dev(float *w32, const float *grad, float *mom, void *w16, long n, const float *d_hyper, float lr_mult,
+                                  float wd_mult, float clip_gradient, const double *d_state, sn_stream_t stream);
 /* fp32 [O][T][I] -> fp16 [I][T][O_pad] (weights for sn_conv_dgrad; O_pad = O rounded up to 8, zero filled). */
 int sn_weight_transpose(const float *w_oti, void *wt_ito_f16, int O, int T, int I, int O_pad, sn_stream_t stream);
 /* The same transposition for MANY weights in one launch (the optimizer step re-emits every data-gradient copy).  desc is a

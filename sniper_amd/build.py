@@ -38,6 +38,7 @@ EXTRA = {
     "voc_segm.hip": ["-ffp-contract=off"],
     "prop_roidb.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
+    "grad_guard.hip": ["-ffp-contract=off"],      # norm, then norm + 1e-6: the state is compared bit for bit with its restatement
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

@@ -1426,6 +1426,26 @@ SN_EXPORT int sn_sgd_mom_update(float *w32, const float *grad, float *mom, void 
   return SN_OK;
 }
 
+// The update statement of the device-hyper kernels, plain and guarded (one copy: the guarded kernels with nothing to apply must give
+// the plain kernels' bits): gr = the gradient as the arena holds it, nm = the new momentum, -> the new master weight.
+__device__ __forceinline__ float sgd_statement(float w, float gr, float m_old, float lr, float wd, float momentum, float rescale,
+                                               float &nm) {
+  const float g = rescale * gr + wd * w;
+  nm = momentum * m_old - lr * g;
+  return w + nm;
+}
+
+// The guarded statement (sn_sgd_mom_update_guarded_dev with a coefficient != 1 or an element-wise clip): the gradient is scaled by the
+// global-norm coefficient, rescaled, clipped to +-clip (clip > 0: mx 'sgd' clips rescale_grad * grad, before weight decay).
+__device__ __forceinline__ float sgd_statement_guarded(float w, float gr, float m_old, float lr, float wd, float momentum, float rescale,
+                                                       float coef, float clip, float &nm) {
+  float u = rescale * (coef * gr);
+  if (clip > 0.f) u = fminf(fmaxf(u, -clip), clip);
+  const float g = u + wd * w;
+  nm = momentum * m_old - lr * g;
+  return w + nm;
+}
+
 // Same update with the per-step hyper-parameters read from device memory (d_hyper = [lr, wd, momentum, rescale]):
 // a launch captured in a hipGraph must not bake the scheduled learning rate into its arguments.
 __global__ __launch_bounds__(256) void sgd_dev_kernel(float *__restrict__ w32, const float *__restrict__ grad,
@@ -1433,11 +1453,9 @@ __global__ __launch_bounds__(256) void sgd_dev_kernel(float *__restrict__ w32, c
                                                       const float *__restrict__ hyper, float lr_mult, float wd_mult) {
   const float lr = hyper[0] * lr_mult, wd = hyper[1] * wd_mult, momentum = hyper[2], rescale = hyper[3];
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float w = w32[i];
-    const float g = rescale * grad[i] + wd * w;
-    const float m = momentum * mom[i] - lr * g;
+    float m;
+    const float nw = sgd_statement(w32[i], grad[i], mom[i], lr, wd, momentum, rescale, m);
     mom[i] = m;
-    const float nw = w + m;
     w32[i] = nw;
     if (w16) w16[i] = (half_t)nw;
   }
@@ -1452,14 +1470,10 @@ __global__ __launch_bounds__(256) void sgd_dev_vec4_kernel(float4 *__restrict__ 
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const float4 w = w32[i], g4 = grad[i], m4 = mom[i];
     float4 nm, nw;
-#define SN_SGD_LANE(f)                                                  \
-    {                                                                   \
-      const float g = rescale * g4.f + wd * w.f;                        \
-      nm.f = momentum * m4.f - lr * g;                                  \
-      nw.f = w.f + nm.f;                                                \
-    }
-    SN_SGD_LANE(x) SN_SGD_LANE(y) SN_SGD_LANE(z) SN_SGD_LANE(w)
-#undef SN_SGD_LANE
+    nw.x = sgd_statement(w.x, g4.x, m4.x, lr, wd, momentum, rescale, nm.x);
+    nw.y = sgd_statement(w.y, g4.y, m4.y, lr, wd, momentum, rescale, nm.y);
+    nw.z = sgd_statement(w.z, g4.z, m4.z, lr, wd, momentum, rescale, nm.z);
+    nw.w = sgd_statement(w.w, g4.w, m4.w, lr, wd, momentum, rescale, nm.w);
     mom[i] = nm;
     w32[i] = nw;
     if (w16) {
@@ -1495,6 +1509,113 @@ SN_EXPORT int sn_sgd_mom_update_dev(float *w32, const float *grad, float *mom, v
     hipLaunchKernelGGL(sgd_dev_vec4_kernel, dim3(ew_blocks(n4)), dim3(256), 0, sn_stream(stream), (float4 *)(w32 + head),
                        (const float4 *)(grad + head), (float4 *)(mom + head), w16 ? (half_t *)w16 + head : (half_t *)nullptr, n4,
                        d_hyper, lr_mult, wd_mult);
+  const long done = head + 4 * n4;
+  if (done < n) scalar(done, n - done);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
+// The same update behind the gradient guard (grad_guard.hip): every thread reads the clipping coefficient and the skip flag from the
+// guard's device state once.  skip: the kernel returns, nothing is written.  coef == 1 and no element-wise clip: the loop of
+// sgd_dev_kernel / sgd_dev_vec4_kernel over sgd_statement, the same bits.  Else the guarded statement.
+__global__ __launch_bounds__(256) void sgd_guard_kernel(float *__restrict__ w32, const float *__restrict__ grad,
+                                                        float *__restrict__ mom, half_t *__restrict__ w16, long n,
+                                                        const float *__restrict__ hyper, float lr_mult, float wd_mult, float clip,
+                                                        const double *__restrict__ state) {
+  if (state[2] != 0.0) return;
+  const float coef = (float)state[1];
+  const float lr = hyper[0] * lr_mult, wd = hyper[1] * wd_mult, momentum = hyper[2], rescale = hyper[3];
+  if (coef == 1.f && !(clip > 0.f)) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+      float m;
+      const float nw = sgd_statement(w32[i], grad[i], mom[i], lr, wd, momentum, rescale, m);
+      mom[i] = m;
+      w32[i] = nw;
+      if (w16) w16[i] = (half_t)nw;
+    }
+    return;
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float m;
+    const float nw = sgd_statement_guarded(w32[i], grad[i], mom[i], lr, wd, momentum, rescale, coef, clip, m);
+    mom[i] = m;
+    w32[i] = nw;
+    if (w16) w16[i] = (half_t)nw;
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_guard_vec4_kernel(float4 *__restrict__ w32, const float4 *__restrict__ grad,
+                                                             float4 *__restrict__ mom, half_t *__restrict__ w16, long n4,
+                                                             const float *__restrict__ hyper, float lr_mult, float wd_mult,
+                                                             float clip, const double *__restrict__ state) {
+  if (state[2] != 0.0) return;
+  const float coef = (float)state[1];
+  const float lr = hyper[0] * lr_mult, wd = hyper[1] * wd_mult, momentum = hyper[2], rescale = hyper[3];
+  // two loops, not one loop with the choice inside: with both statements in one body the compiler shares their sub-expressions and
+  // contracts the plain one differently from sgd_dev_vec4_kernel -- one ulp, where the same bits are promised
+  if (coef == 1.f && !(clip > 0.f)) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+      const float4 w = w32[i], g4 = grad[i], m4 = mom[i];
+      float4 nm, nw;
+      nw.x = sgd_statement(w.x, g4.x, m4.x, lr, wd, momentum, rescale, nm.x);
+      nw.y = sgd_statement(w.y, g4.y, m4.y, lr, wd, momentum, rescale, nm.y);
+      nw.z = sgd_statement(w.z, g4.z, m4.z, lr, wd, momentum, rescale, nm.z);
+      nw.w = sgd_statement(w.w, g4.w, m4.w, lr, wd, momentum, rescale, nm.w);
+      mom[i] = nm;
+      w32[i] = nw;
+      if (w16) {
+        half4 h;
+        h[0] = (half_t)nw.x; h[1] = (half_t)nw.y; h[2] = (half_t)nw.z; h[3] = (half_t)nw.w;
+        *reinterpret_cast<half4 *>(w16 + 4 * i) = h;
+      }
+    }
+    return;
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 w = w32[i], g4 = grad[i], m4 = mom[i];
+    float4 nm, nw;
+    nw.x = sgd_statement_guarded(w.x, g4.x, m4.x, lr, wd, momentum, rescale, coef, clip, nm.x);
+    nw.y = sgd_statement_guarded(w.y, g4.y, m4.y, lr, wd, momentum, rescale, coef, clip, nm.y);
+    nw.z = sgd_statement_guarded(w.z, g4.z, m4.z, lr, wd, momentum, rescale, coef, clip, nm.z);
+    nw.w = sgd_statement_guarded(w.w, g4.w, m4.w, lr, wd, momentum, rescale, coef, clip, nm.w);
+    mom[i] = nm;
+    w32[i] = nw;
+    if (w16) {
+      half4 h;
+      h[0] = (half_t)nw.x; h[1] = (half_t)nw.y; h[2] = (half_t)nw.z; h[3] = (half_t)nw.w;
+      *reinterpret_cast<half4 *>(w16 + 4 * i) = h;
+    }
+  }
+}
+
+SN_EXPORT int sn_sgd_mom_update_guarded_dev(float *w32, const float *grad, float *mom, void *w16, long n, const float *d_hyper,
+                                            float lr_mult, float wd_mult, float clip_gradient, const double *d_state,
+                                            sn_stream_t stream) {
+  SN_REQUIRE(w32 && grad && mom && d_hyper && d_state && n >= 0, "sn_sgd_mom_update_guarded_dev: bad arguments");
+  SN_REQUIRE(clip_gradient == clip_gradient, "sn_sgd_mom_update_guarded_dev: clip_gradient is NaN");
+  SN_REQUIRE(((uintptr_t)d_state & 7) == 0, "sn_sgd_mom_update_guarded_dev: d_state must be 8-byte aligned");
+  if (n == 0) return SN_OK;
+  // the head / four-wide body / tail split of sn_sgd_mom_update_dev
+  auto scalar = [&](long from, long count) {
+    hipLaunchKernelGGL(sgd_guard_kernel, dim3(ew_blocks(count)), dim3(256), 0, sn_stream(stream), w32 + from, grad + from,
+                       mom + from, w16 ? (half_t *)w16 + from : (half_t *)nullptr, count, d_hyper, lr_mult, wd_mult, clip_gradient,
+                       d_state);
+  };
+  long head = (long)(((16 - ((uintptr_t)w32 & 15)) & 15) / 4);
+  if (head > n) head = n;
+  const bool same = (((uintptr_t)(w32 + head) | (uintptr_t)(grad + head) | (uintptr_t)(mom + head)) & 15) == 0 &&
+                    (w16 == nullptr || ((uintptr_t)((half_t *)w16 + head) & 7) == 0);
+  if (!same) {
+    scalar(0, n);
+    SN_CHECK_LAUNCH();
+    return SN_OK;
+  }
+  if (head > 0) scalar(0, head);
+  const long n4 = (n - head) / 4;
+  if (n4 > 0)
+    hipLaunchKernelGGL(sgd_guard_vec4_kernel, dim3(ew_blocks(n4)), dim3(256), 0, sn_stream(stream), (float4 *)(w32 + head),
+                       (const float4 *)(grad + head), (float4 *)(mom + head), w16 ? (half_t *)w16 + head : (half_t *)nullptr, n4,
+                       d_hyper, lr_mult, wd_mult, clip_gradient, d_state);
   const long done = head + 4 * n4;
   if (done < n) scalar(done, n - done);
   SN_CHECK_LAUNCH();

@@ -259,6 +259,7 @@ class Executor(object):
         self._capture_stream = None   # forward: the side stream the test-time forward is captured on
         self._pinned_inputs = {}      # load_inputs: input name -> ring of pinned host buffers
         self._hyper_host = None       # update: the values self.hyper holds
+        self.guard = None             # set_grad_guard: thresholds, device state and workspace of the gradient guard
         self._lower()
         self._mark_half_region()
         self.split_k = self._choose_split() if (split_backward and for_training) else 0
@@ -1004,8 +1005,38 @@ class Executor(object):
         self._eager_fb += 1
         return self.outputs
 
+    def set_grad_guard(self, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False):
+        """The gradient guard of the optimizer pass (DESIGN.md "Gradient guard"): before the update one sn_grad_guard reads the whole
+        gradient arena -- norm of rescale_grad * grad over its finite elements, number of non-finite ones -- into eight doubles of
+        device state, and the update of every group consults them (sn_sgd_mom_update_guarded_dev): a step with a non-finite gradient
+        writes nothing (skip_nonfinite), the gradients are scaled so that their global norm is at most clip_global_norm, and
+        rescale_grad * grad is clipped element-wise to +-clip_gradient (mx 'sgd').  All of it inside the captured optimizer graph,
+        no host synchronisation; the thresholds are launch arguments, fixed until the next call.  Nothing set: the guard is off
+        and the update is the plain one.  An optimizer graph already captured is dropped and captured again."""
+        for name, v in (('clip_gradient', clip_gradient), ('clip_global_norm', clip_global_norm)):
+            if v is not None and not float(v) > 0.0:
+                raise ValueError('%s must be None or > 0, got %r' % (name, v))
+        self._graph_up = None
+        if clip_gradient is None and clip_global_norm is None and not skip_nonfinite:
+            self.guard = None
+            return
+        n = self.arena_grad.numel()
+        self.guard = {'clip_gradient': float(clip_gradient or 0.0), 'clip_global_norm': float(clip_global_norm or 0.0),
+                      'skip_nonfinite': int(bool(skip_nonfinite)),
+                      'state': self.zeros((8,), torch.float64),
+                      'ws': self.empty((max(int(hip.query('sn_grad_guard_workspace_bytes', n, 0)), 256),), torch.uint8)}
+
     def _update_body(self, lr=None, wd=None, momentum=None, rescale_grad=None):
+        g = self.guard
+        if g is not None:
+            hip.call('sn_grad_guard', self.arena_grad, self.arena_grad.numel(), self.hyper, g['clip_global_norm'], g['skip_nonfinite'],
+                     0, g['ws'], g['state'], hip.stream())
         for (lr_mult, wd_mult, _half), a, b in self.groups:
+            if g is not None:
+                hip.call('sn_sgd_mom_update_guarded_dev', self.arena_master[a:], self.arena_grad[a:], self.arena_mom[a:],
+                         self.arena_w16[a:], b - a, self.hyper, float(lr_mult), float(wd_mult), g['clip_gradient'], g['state'],
+                         hip.stream())
+                continue
             hip.call('sn_sgd_mom_update_dev', self.arena_master[a:], self.arena_grad[a:], self.arena_mom[a:], self.arena_w16[a:],
                      b - a, self.hyper, float(lr_mult), float(wd_mult), hip.stream())
         self.refresh_compute_copies(only_trainable=True)

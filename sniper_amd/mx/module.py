@@ -143,6 +143,7 @@ class Module(object):
                     ex.refresh_compute_copies()                  # the values are there: only this shape's derived buffers
                 else:
                     ex.set_params(self._arg_params, self._aux_params)
+            self._guard_exe(ex)
             self._exes[key] = ex
             if not self.for_training:
                 self._evict_stale(keep=ex)
@@ -254,12 +255,121 @@ class Module(object):
         if optimizer != 'sgd':
             raise NotImplementedError('optimizer %r (the reference trains with sgd)' % (optimizer,))
         op = dict(optimizer_params)
+        guard = self._guard_options(op)
         self.opt = {'lr': float(op.get('learning_rate', 0.01)), 'wd': float(op.get('wd', 0.0)),
                     'momentum': float(op.get('momentum', 0.0)), 'rescale_grad': float(op.get('rescale_grad', 1.0)),
                     'lr_scheduler': op.get('lr_scheduler')}
+        self.opt.update(guard)
         if self.opt['lr_scheduler'] is not None:
             self.opt['lr_scheduler'].base_lr = self.opt['lr']
         self.optimizer_initialized = True
+        self._guard_host = None
+        for ex in getattr(self, '_exes', {}).values():
+            self._guard_exe(ex)
+
+    # ---- gradient guard (Executor.set_grad_guard): clip_gradient is mx 'sgd's parameter; clip_global_norm, skip_nonfinite and
+    # max_consecutive_skips are this engine's
+    @staticmethod
+    def _guard_options(op):
+        out = {}
+        for key in ('clip_gradient', 'clip_global_norm'):
+            v = op.get(key)
+            if v is not None:
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not float(v) > 0.0:
+                    raise ValueError('optimizer parameter %s must be None or a number > 0, got %r' % (key, v))
+                v = float(v)
+            out[key] = v
+        v = op.get('skip_nonfinite', False)
+        if not isinstance(v, (bool, np.bool_)) and v not in (0, 1):
+            raise ValueError('optimizer parameter skip_nonfinite must be a bool, got %r' % (v,))
+        out['skip_nonfinite'] = bool(v)
+        v = op.get('max_consecutive_skips', 16)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError('optimizer parameter max_consecutive_skips must be None or an int >= 1, got %r' % (v,))
+            v = int(v)
+        out['max_consecutive_skips'] = v
+        out['guard'] = out['clip_gradient'] is not None or out['clip_global_norm'] is not None or out['skip_nonfinite']
+        return out
+
+    def _guard_exe(self, ex):
+        """the optimizer's guard options -> a training executor (at init_optimizer for the bound ones, at bind for later ones)"""
+        opt = getattr(self, 'opt', None)
+        if opt is None or not ex.for_training:
+            return
+        if opt['guard'] or ex.guard is not None:
+            ex.set_grad_guard(opt['clip_gradient'], opt['clip_global_norm'], opt['skip_nonfinite'])
+
+    _GUARD_KEYS = ('norm', 'coef', 'skipped_last', 'nonfinite', 'steps', 'skipped', 'consecutive', 'sumsq')
+
+    @classmethod
+    def _guard_dict(cls, s):
+        return dict(zip(cls._GUARD_KEYS, (float(s[0]), float(s[1]), bool(s[2]), int(s[3]), int(s[4]), int(s[5]), int(s[6]), float(s[7]))))
+
+    def grad_guard_state(self, wait=True):
+        """The guard's device state as a dict (norm and sumsq in the arena's units: with TRAIN.fp16 the gradients carry the static
+        loss scale), None when the guard is off.  wait=True reads the device now (waits for the steps enqueued so far);
+        wait=False returns the newest snapshot that has already landed on the host -- one or two steps old -- or None before the first."""
+        g = self.exe.guard if getattr(self, 'exe', None) is not None else None
+        if g is None:
+            return None
+        if wait:
+            return self._guard_dict(g['state'].cpu().tolist())
+        host = getattr(self, '_guard_host', None)
+        if host is None:
+            return None
+        landed = [s['host'].tolist() for s in host['slots'] if s['event'] is not None and s['event'].query()]
+        if host['last'] is not None:
+            landed.append(host['last'])
+        return self._guard_dict(max(landed, key=lambda s: s[4])) if landed else None      # (looks only: update() does the inspecting)
+
+    def _guard_snapshot(self):
+        """After a guarded step has been enqueued: its 64 bytes of state -> pinned host memory without waiting (a device copy on the
+        step's stream -- the next step rewrites the state --, the device -> host copy on a side stream behind an event, as
+        _snapshot_for_metric does for the outputs); then whatever EARLIER snapshot has landed is inspected: a skipped step is logged
+        once, max_consecutive_skips skipped steps in a row raise FloatingPointError.  Never waits for the device."""
+        g = self.exe.guard
+        host = getattr(self, '_guard_host', None)
+        if host is None:
+            host = self._guard_host = {
+                'stream': torch.cuda.Stream(device=self._device), 'k': 0, 'last': None, 'skipped': 0, 'steps': 0,
+                'slots': [{'dev': torch.zeros_like(g['state']), 'host': torch.zeros(8, dtype=torch.float64, pin_memory=True),
+                           'event': None, 'fresh': False} for _ in range(2)]}
+        self._guard_poll(host)                                 # (before the older slot is reused)
+        slot = host['slots'][host['k'] & 1]
+        host['k'] += 1
+        main = torch.cuda.current_stream(self._device)
+        if slot['event'] is not None:
+            main.wait_event(slot['event'])                     # device-side: the slot's previous copy out has read slot['dev']
+        slot['dev'].copy_(g['state'])
+        cloned = torch.cuda.Event()
+        cloned.record(main)
+        side = host['stream']
+        side.wait_event(cloned)
+        with torch.cuda.stream(side):
+            slot['host'].copy_(slot['dev'], non_blocking=True)
+            slot['event'] = torch.cuda.Event()
+            slot['event'].record(side)
+        slot['fresh'] = True
+
+    def _guard_poll(self, host):
+        for slot in sorted((s for s in host['slots'] if s['fresh'] and s['event'].query()), key=lambda s: float(s['host'][4])):
+            slot['fresh'] = False
+            s = slot['host'].tolist()
+            if s[4] <= host['steps']:
+                continue
+            host['last'], host['steps'] = s, s[4]
+            if s[5] > host['skipped']:
+                host['skipped'] = s[5]
+                if s[2]:
+                    self.logger.warning('gradient guard: step %d skipped, %d non-finite gradient elements, norm of the finite rest %g '
+                                        '(%d skipped of %d steps, %d in a row)', int(s[4]), int(s[3]), s[0], int(s[5]), int(s[4]), int(s[6]))
+                else:
+                    self.logger.warning('gradient guard: %d of %d steps skipped so far', int(s[5]), int(s[4]))
+            limit = self.opt.get('max_consecutive_skips')
+            if limit is not None and s[6] >= limit:
+                raise FloatingPointError('gradient guard: %d consecutive steps skipped for non-finite gradients (step %d, %d non-finite '
+                                         'elements in the last one); max_consecutive_skips = %d' % (int(s[6]), int(s[4]), int(s[3]), limit))
 
     # ---- compute
     def _adopt_iterator(self, train_data):
@@ -386,7 +496,10 @@ class Module(object):
                 self._comm_event = None
         sched = self.opt['lr_scheduler']
         lr = sched(self.exe.num_update + 1) if sched is not None else self.opt['lr']
+        # (the guard, when set, is the first thing the optimizer pass runs: behind the all-reduce, so every rank decides on the same sum)
         self.exe.update(lr, self.opt['wd'], self.opt['momentum'], self.opt['rescale_grad'])
+        if self.exe.guard is not None:
+            self._guard_snapshot()
 
     def get_outputs(self, merge_multi_context=True):
         """The executor's output tensors, NOT copies: a test-time executor replays a captured forward into the same tensors, so

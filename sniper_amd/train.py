@@ -21,11 +21,14 @@ def fixed_param_names(cfg, sym):
 def optimizer_params(cfg, lr_scheduler=None):
     """lib/train_utils/utils.py:13-42: fp16 folds the static loss scale into lr and wd."""
     tr = cfg.TRAIN
+    # the gradient guard (Module.init_optimizer): three keys the reference's configs do not have -- absent means off.  With fp16 the
+    # arena holds gradients multiplied by the static loss scale: the two thresholds are in those units.
+    guard = {'clip_gradient': getattr(tr, 'CLIP_GRADIENT', None), 'clip_global_norm': getattr(tr, 'CLIP_GLOBAL_NORM', None),
+             'skip_nonfinite': bool(getattr(tr, 'SKIP_NONFINITE', False))}
     if tr.fp16:
-        return {'momentum': tr.momentum, 'wd': tr.wd * tr.scale, 'learning_rate': tr.lr / tr.scale, 'rescale_grad': 1.0,
-                'multi_precision': True, 'clip_gradient': None, 'lr_scheduler': lr_scheduler}
-    return {'momentum': tr.momentum, 'wd': tr.wd, 'learning_rate': tr.lr, 'rescale_grad': 1.0, 'clip_gradient': None,
-            'lr_scheduler': lr_scheduler}
+        return dict({'momentum': tr.momentum, 'wd': tr.wd * tr.scale, 'learning_rate': tr.lr / tr.scale, 'rescale_grad': 1.0,
+                     'multi_precision': True, 'lr_scheduler': lr_scheduler}, **guard)
+    return dict({'momentum': tr.momentum, 'wd': tr.wd, 'learning_rate': tr.lr, 'rescale_grad': 1.0, 'lr_scheduler': lr_scheduler}, **guard)
 
 
 class Trainer(object):
@@ -38,12 +41,21 @@ class Trainer(object):
     included, through the max-pool backward -- except bn_data, which stays folded into the image packing whatever the list says
     (MXNet would train bn_data_beta; that needs the stem's data gradient, which is never computed here).
     `ohem=k` trains with online hard example mining (TRAIN.ENABLE_OHEM = True, TRAIN.BATCH_ROIS_OHEM = k): per chip the k RoIs of
-    largest loss carry the R-CNN losses, on the device, inside the replayed step (None keeps the config's two keys)."""
+    largest loss carry the R-CNN losses, on the device, inside the replayed step (None keeps the config's two keys).
+    `clip_gradient`, `clip_global_norm`, `skip_nonfinite` turn the gradient guard of the optimizer pass on (TRAIN.CLIP_GRADIENT,
+    TRAIN.CLIP_GLOBAL_NORM, TRAIN.SKIP_NONFINITE; Module.init_optimizer): a step whose gradients hold inf / NaN is skipped, the rest is
+    clipped -- thresholds in the arena's units, i.e. times TRAIN.scale with fp16."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
-                 fix_bn=False, fixed_params=None, ohem=None):
+                 fix_bn=False, fixed_params=None, ohem=None, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
+        if clip_gradient is not None:
+            cfg.TRAIN.CLIP_GRADIENT = clip_gradient
+        if clip_global_norm is not None:
+            cfg.TRAIN.CLIP_GLOBAL_NORM = clip_global_norm
+        if skip_nonfinite:
+            cfg.TRAIN.SKIP_NONFINITE = True
         if fixed_params is not None:
             cfg.network.FIXED_PARAMS = list(fixed_params)
         if ohem is not None:
