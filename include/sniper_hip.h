@@ -903,6 +903,38 @@ int sn_grad_guard(const float *d_grad, long n, const float *d_hyper, float clip_
                   void *d_ws, double *d_state, sn_stream_t stream);
 int sn_sgd_mom_update_guarded_dev(float *w32, const float *grad, float *mom, void *w16, long n, const float *d_hyper, float lr_mult,
                                   float wd_mult, float clip_gradient, const double *d_state, sn_stream_t stream);
+/* Dynamic loss scaling of the fp16 training step: the scale lives on the device, the loss-gradient kernels of the captured
+ * forward/backward read it, the guard of the captured optimizer pass unscales with it and moves it.  No host synchronisation.
+ * d_ls, eight doubles (8-byte aligned; the caller writes [0] ONCE -- a power of two within 2^-126 .. 2^127 -- and zeroes the rest):
+ *     [0] scale: what the loss kernels of the NEXT forward multiply with; always a power of two
+ *     [1] scale_used: the scale the gradients just judged carry ([0] as it was before this step's finalize)
+ *     [2] clean steps since the scale last changed      [3] growths so far (the scale went up)      [4] back-offs so far (it went down)
+ *     [5] steps at which growth was due but max_scale held it (S * growth_factor > max_scale)
+ *     [6] steps at which back-off was due but min_scale held it (S * backoff_factor < min_scale)      [7] reserved (0)
+ * sn_softmax_output_bwd_scaled: sn_softmax_output_bwd with grad_scale * (float)d_ls[0] in place of grad_scale (every thread reads
+ *   d_ls[0] once); both paths, chosen by the same rule.  sn_fill_scaled_f32: out[i] = value * (float)d_ls[0], the MakeLoss gradient.
+ *   For d_ls[0] = S both give the bits of the plain kernels called with grad_scale * S (S is a power of two).
+ * sn_grad_guard_scaled: the partial pass of sn_grad_guard (the same kernel, grid, workspace), then a single-block finalize.  With
+ *   S = d_ls[0] on entry it writes d_state as sn_grad_guard does, except
+ *     [0] norm = sqrt(sumsq) * fabs((double)d_hyper[3]) / S  (true units)
+ *     [1] coef = c / S, c = clip_global_norm > 0 ? min(1, clip_global_norm / (norm + 1e-6)) : 1 -- what sn_sgd_mom_update_guarded_dev
+ *         (used unchanged) multiplies the gradients with: it clips and unscales in one product
+ *     [2] skip = nonfinite > 0 (dynamic scaling implies skip_nonfinite);      [7] sumsq stays in arena units
+ *   and then moves the scale: d_ls[1] = S; skip: scale = max(S * backoff_factor, min_scale), clean = 0; else clean += 1 and, if
+ *   growth_interval > 0 and clean == growth_interval, scale = min(S * growth_factor, max_scale), clean = 0 (growth_interval 0: never).
+ *   Refused before any launch: what sn_grad_guard refuses; a factor or a bound that is not a positive power of two; growth_factor < 1;
+ *   backoff_factor > 1; min_scale > max_scale or either outside 2^-126 .. 2^127; growth_interval < 0; a null or misaligned d_ls.
+ * sn_aux_shadow: desc = DEVICE table of n_desc records {float *ptr; int32_t off; int32_t n} (16 bytes each, 8-byte aligned), the
+ *   vectors a training forward writes as a side effect (moving_mean / moving_var of every batch-statistics BatchNorm).  mode 0 saves:
+ *   d_shadow[off + i] = ptr[i], i < n.  mode 1 restores: if d_state[2] != 0 (the guard skipped the step) ptr[i] = d_shadow[off + i],
+ *   else nothing is written.  One launch, one block per record; nothing outside the named ranges is read or written; n_desc = 0: no launch. */
+int sn_softmax_output_bwd_scaled(const float *p, const float *label, float *grad, long outer, int K, long inner, float ignore_label,
+                                 int use_ignore, float grad_scale, int normalize_valid, int *ws, const double *d_ls, sn_stream_t stream);
+int sn_fill_scaled_f32(float *out, long n, float value, const double *d_ls, sn_stream_t stream);
+int sn_grad_guard_scaled(const float *d_grad, long n, const float *d_hyper, float clip_global_norm, int max_blocks, int growth_interval,
+                         double growth_factor, double backoff_factor, double min_scale, double max_scale, void *d_ws, double *d_state,
+                         double *d_ls, sn_stream_t stream);
+int sn_aux_shadow(const void *desc, int n_desc, float *d_shadow, int mode, const double *d_state, sn_stream_t stream);
 /* fp32 [O][T][I] -> fp16 [I][T][O_pad] (weights for sn_conv_dgrad; O_pad = O rounded up to 8, zero filled). */
 int sn_weight_transpose(const float *w_oti, void *wt_ito_f16, int O, int T, int I, int O_pad, sn_stream_t stream);
 /* The same transposition for MANY weights in one launch (the optimizer step re-emits every data-gradient copy).  desc is a

@@ -12,17 +12,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "grad_guard.h"
 
 namespace {
-
-constexpr int kThreads = 256;                 // threads per block
-constexpr int kVec = 4;                       // 16-byte loads per lane per trip
-constexpr int kElems = 4 * kVec;              // floats per thread per trip
-constexpr int kSpan = kThreads * kElems;      // floats per block per trip
-constexpr int kDefaultBlocks = 1024;          // the library's grid cap (max_blocks = 0)
-constexpr int kMaxBlocks = 65535;
-constexpr int kStateDoubles = 8;
-constexpr int kChunk = 1024;                  // partials per round of the finalize block
 
 // non-finite <=> !(|g| <= FLT_MAX): counted and left out of the sum (adding 0.0 is exact)
 __device__ __forceinline__ void guard_take(float g, double &s, unsigned &c) {
@@ -90,43 +82,9 @@ __global__ __launch_bounds__(kThreads) void grad_guard_finalize_kernel(const dou
                                                                        const unsigned long long *__restrict__ pcnt, int nblk,
                                                                        const float *__restrict__ hyper, float clip_global_norm,
                                                                        int skip_nonfinite, double *__restrict__ state) {
-  __shared__ double ls[kChunk];
-  __shared__ unsigned long long lc[kChunk];
-  __shared__ unsigned long long bad_total;
-  double sumsq = 0.0;
-  unsigned long long bad = 0;
-  for (int b0 = 0; b0 < nblk; b0 += kChunk) {
-    const int m = nblk - b0 < kChunk ? nblk - b0 : kChunk;
-    for (int i = threadIdx.x; i < kChunk; i += kThreads) {      // (zeros behind the last partial: a round is whole groups of eight)
-      ls[i] = i < m ? psum[b0 + i] : 0.0;
-      lc[i] = i < m ? pcnt[b0 + i] : 0ull;
-    }
-    __syncthreads();
-    // one lane adds the sums in index order, the first lane of the next wave the counts beside it; eight LDS reads are issued
-    // before the eight dependent additions (one read, one wait, one addition at a time was most of this launch)
-    if (threadIdx.x == 0) {
-      for (int i = 0; i < m; i += 8) {
-        double v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ls[i + j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sumsq += v[j];
-      }
-    } else if (threadIdx.x == kWave) {
-      for (int i = 0; i < m; i += 8) {
-        unsigned long long v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = lc[i + j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bad += v[j];
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == kWave) bad_total = bad;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  bad = bad_total;
+  double sumsq;
+  unsigned long long bad;
+  if (!guard_sum_partials(psum, pcnt, nblk, sumsq, bad)) return;
   const double norm = sqrt(sumsq) * fabs((double)hyper[3]);
   double coef = 1.0;
   if (clip_global_norm > 0.f) {
@@ -142,12 +100,6 @@ __global__ __launch_bounds__(kThreads) void grad_guard_finalize_kernel(const dou
   state[5] += skip;
   state[6] = skip != 0.0 ? state[6] + 1.0 : 0.0;
   state[7] = sumsq;
-}
-
-int guard_blocks(long n, int max_blocks) {
-  const long cap = max_blocks > 0 ? max_blocks : kDefaultBlocks;
-  const long b = (n + kSpan - 1) / kSpan;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 }  // namespace
@@ -166,21 +118,35 @@ SN_EXPORT size_t sn_grad_guard_workspace_bytes(long n, int max_blocks) {
   return sn_align((size_t)guard_blocks(n, max_blocks) * (sizeof(double) + sizeof(unsigned long long)));
 }
 
-SN_EXPORT int sn_grad_guard(const float *d_grad, long n, const float *d_hyper, float clip_global_norm, int skip_nonfinite,
-                            int max_blocks, void *d_ws, double *d_state, sn_stream_t stream) {
-  SN_REQUIRE(d_grad && d_hyper && d_ws && d_state, "sn_grad_guard: null pointer");
-  SN_REQUIRE(n >= 0, "sn_grad_guard: n = %ld", n);
-  SN_REQUIRE(clip_global_norm >= 0.f, "sn_grad_guard: clip_global_norm must be >= 0 (0 = off) and not NaN");
-  SN_REQUIRE(max_blocks >= 0 && max_blocks <= kMaxBlocks, "sn_grad_guard: max_blocks = %d outside 0 .. %d", max_blocks, kMaxBlocks);
+// the argument checks and the partial pass of sn_grad_guard and sn_grad_guard_scaled (loss_scale.hip): the same kernel, grid, workspace
+int sn_grad_guard_partials(const char *who, const float *d_grad, long n, const float *d_hyper, float clip_global_norm, int max_blocks,
+                           void *d_ws, double *d_state, int *nblk_out, hipStream_t s) {
+  SN_REQUIRE(d_grad && d_hyper && d_ws && d_state, "%s: null pointer", who);
+  SN_REQUIRE(n >= 0, "%s: n = %ld", who, n);
+  SN_REQUIRE(clip_global_norm >= 0.f, "%s: clip_global_norm must be >= 0 (0 = off) and not NaN", who);
+  SN_REQUIRE(max_blocks >= 0 && max_blocks <= kMaxBlocks, "%s: max_blocks = %d outside 0 .. %d", who, max_blocks, kMaxBlocks);
   SN_REQUIRE(((uintptr_t)d_grad & 3) == 0 && ((uintptr_t)d_ws & 7) == 0 && ((uintptr_t)d_state & 7) == 0,
-             "sn_grad_guard: d_grad must be 4-byte aligned, d_ws and d_state 8-byte aligned");
+             "%s: d_grad must be 4-byte aligned, d_ws and d_state 8-byte aligned", who);
   const int nblk = guard_blocks(n, max_blocks);
   long head = (long)(((16 - ((uintptr_t)d_grad & 15)) & 15) / 4);
   if (head > n) head = n;
   const long n4 = (n - head) / 4;
   double *psum = (double *)d_ws;
   unsigned long long *pcnt = (unsigned long long *)(psum + nblk);
-  hipLaunchKernelGGL(grad_guard_partial_kernel, dim3(nblk), dim3(kThreads), 0, sn_stream(stream), d_grad, n, head, n4, psum, pcnt);
+  hipLaunchKernelGGL(grad_guard_partial_kernel, dim3(nblk), dim3(kThreads), 0, s, d_grad, n, head, n4, psum, pcnt);
+  SN_CHECK_LAUNCH();
+  *nblk_out = nblk;
+  return SN_OK;
+}
+
+SN_EXPORT int sn_grad_guard(const float *d_grad, long n, const float *d_hyper, float clip_global_norm, int skip_nonfinite,
+                            int max_blocks, void *d_ws, double *d_state, sn_stream_t stream) {
+  int nblk = 0;
+  const int rc = sn_grad_guard_partials("sn_grad_guard", d_grad, n, d_hyper, clip_global_norm, max_blocks, d_ws, d_state, &nblk,
+                                        sn_stream(stream));
+  if (rc != SN_OK) return rc;
+  double *psum = (double *)d_ws;
+  unsigned long long *pcnt = (unsigned long long *)(psum + nblk);
   hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(kThreads), 0, sn_stream(stream), (const double *)psum,
                      (const unsigned long long *)pcnt, nblk, d_hyper, clip_global_norm, skip_nonfinite ? 1 : 0, d_state);
   SN_CHECK_LAUNCH();

@@ -7,6 +7,7 @@
 // pixel stride so that producers can write into slices of a wider buffer (free Concat).
 // Roofline: every kernel here is bound by HBM bytes; all global accesses are 16 bytes per lane.
 #include "common.h"
+#include "softmax_grad.h"
 #include <algorithm>
 
 // ---------------------------------------------------------------------------------------------
@@ -1210,22 +1211,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float *__restric
                                                           float *__restrict__ g, long outer, int K, long inner,
                                                           float ignore, int use_ignore, float grad_scale, int normalize_valid,
                                                           const int *__restrict__ valid_count) {
-  const long total = outer * inner;
-  float mul = grad_scale;
-  if (normalize_valid) {
-    const int vc = *valid_count;
-    mul = grad_scale / (float)(vc > 1 ? vc : 1);
-  }
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long o = i / inner, s = i - o * inner;
-    const float l = label[i];
-    const bool ign = use_ignore && l == ignore;
-    const int li = (int)l;
-    for (int k = 0; k < K; ++k) {
-      const long idx = o * K * inner + (long)k * inner + s;
-      g[idx] = ign ? 0.f : mul * (p[idx] - (k == li ? 1.f : 0.f));
-    }
-  }
+  softmax_bwd_strided(p, label, g, outer, K, inner, ignore, use_ignore, softmax_grad_mul(grad_scale, normalize_valid, valid_count));
 }
 
 // ---- inner == 1 (the R-CNN classifier: 6000 rows of 81): with one thread per row the kernels above read and write with a stride
@@ -1233,14 +1219,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float *__restric
 // R consecutive rows, i.e. one contiguous range of memory: 16-byte coalesced loads bring it into LDS (row pitch K | 1 floats, odd,
 // so that the lanes of the row pass hit different banks), thread r runs THE SAME statements in the same order as softmax_fwd_kernel
 // over its row in LDS -- the result is bit-identical, tests/test_gpu_softmax_rows.py -- and the block goes back out coalesced.
-// R is a multiple of 4 (every block starts 16-byte aligned) and at most 64 (6000 rows -> 94 workgroups).
-constexpr int kSoftmaxRowsMax = 64, kSoftmaxLdsFloats = 16384;      // 64 KB of LDS at most
-static int softmax_rows_per_block(int K) { return std::min(kSoftmaxRowsMax, kSoftmaxLdsFloats / (K | 1)) & ~3; }
-// the row path: contiguous rows, a block of at least 16 of them in LDS (K <= 1023), 16-byte aligned tensors
-static bool softmax_rows_ok(const void *a, const void *b, int K, long inner) {
-  return inner == 1 && softmax_rows_per_block(K) >= 16 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 &&
-         sn_debug_get(SN_OPT_SOFTMAX_STRIDED) == 0;
-}
+// R is a multiple of 4 (every block starts 16-byte aligned) and at most 64 (6000 rows -> 94 workgroups): softmax_grad.h.
 
 __global__ __launch_bounds__(256) void softmax_rows_fwd_kernel(const float *__restrict__ x, float *__restrict__ p, long outer, int K,
                                                                int R, SnDiv dK) {
@@ -1297,37 +1276,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float *__re
                                                                float *__restrict__ g, long outer, int K, int R, SnDiv dK, float ignore,
                                                                int use_ignore, float grad_scale, int normalize_valid,
                                                                const int *__restrict__ valid_count) {
-  float mul = grad_scale;
-  if (normalize_valid) {
-    const int vc = *valid_count;
-    mul = grad_scale / (float)(vc > 1 ? vc : 1);
-  }
-  const long row0 = (long)blockIdx.x * R;
-  const int nr = (int)(outer - row0 < R ? outer - row0 : R);
-  const int n = nr * K, n4 = n >> 2;
-  const float *pb = p + row0 * K, *lb = label + row0;
-  float *gb = g + row0 * K;
-  auto one = [&](float pv, unsigned r, unsigned k) {
-    const float l = lb[r];
-    const bool ign = use_ignore && l == ignore;
-    const int li = (int)l;
-    return ign ? 0.f : mul * (pv - ((int)k == li ? 1.f : 0.f));
-  };
-  for (int v = threadIdx.x; v < n4; v += 256) {
-    const float4 f = reinterpret_cast<const float4 *>(pb)[v];
-    float e[4] = {f.x, f.y, f.z, f.w};
-    unsigned k, r = sn_divmod(4u * v, dK, k);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      e[j] = one(e[j], r, k);
-      if (++k == (unsigned)K) { k = 0; ++r; }
-    }
-    reinterpret_cast<float4 *>(gb)[v] = make_float4(e[0], e[1], e[2], e[3]);
-  }
-  for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) {
-    unsigned k, r = sn_divmod((unsigned)i, dK, k);
-    gb[i] = one(pb[i], r, k);
-  }
+  softmax_bwd_rows(p, label, g, outer, K, R, dK, ignore, use_ignore, softmax_grad_mul(grad_scale, normalize_valid, valid_count));
 }
 
 SN_EXPORT int sn_softmax_fwd(const float *x, float *p, long outer, int K, long inner, sn_stream_t stream) {
@@ -1344,6 +1293,14 @@ SN_EXPORT int sn_softmax_fwd(const float *x, float *p, long outer, int K, long i
   return SN_OK;
 }
 
+// ws[0] = the number of labels that are not ignored (softmax_grad.h: shared with the device-scaled gradient of loss_scale.hip)
+int sn_softmax_count_valid(const float *label, long n, float ignore_label, int use_ignore, int *ws, hipStream_t s) {
+  SN_HIP(hipMemsetAsync(ws, 0, sizeof(int), s));
+  hipLaunchKernelGGL(count_valid_kernel, dim3(sn_blocks(n, 256)), dim3(256), 0, s, label, n, use_ignore ? ignore_label : -1e30f, ws);
+  SN_CHECK_LAUNCH();
+  return SN_OK;
+}
+
 // ws: one int (valid-label counter)
 SN_EXPORT int sn_softmax_output_bwd(const float *p, const float *label, float *grad, long outer, int K, long inner,
                                     float ignore_label, int use_ignore, float grad_scale, int normalize_valid, int *ws,
@@ -1351,10 +1308,8 @@ SN_EXPORT int sn_softmax_output_bwd(const float *p, const float *label, float *g
   SN_REQUIRE(p && label && grad && ws, "sn_softmax_output_bwd: null pointer");
   hipStream_t s = sn_stream(stream);
   if (normalize_valid) {
-    SN_HIP(hipMemsetAsync(ws, 0, sizeof(int), s));
-    hipLaunchKernelGGL(count_valid_kernel, dim3(sn_blocks(outer * inner, 256)), dim3(256), 0, s, label, outer * inner,
-                       use_ignore ? ignore_label : -1e30f, ws);
-    SN_CHECK_LAUNCH();
+    const int rc = sn_softmax_count_valid(label, outer * inner, ignore_label, use_ignore, ws, s);
+    if (rc != SN_OK) return rc;
   }
   if (softmax_rows_ok(p, grad, K, inner)) {
     const int R = softmax_rows_per_block(K);

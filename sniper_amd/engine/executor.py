@@ -260,6 +260,7 @@ class Executor(object):
         self._pinned_inputs = {}      # load_inputs: input name -> ring of pinned host buffers
         self._hyper_host = None       # update: the values self.hyper holds
         self.guard = None             # set_grad_guard: thresholds, device state and workspace of the gradient guard
+        self.loss_scale = None        # set_loss_scale: policy, device scaler state, table and shadow of the forward's side effects
         self._lower()
         self._mark_half_region()
         self.split_k = self._choose_split() if (split_backward and for_training) else 0
@@ -853,6 +854,10 @@ class Executor(object):
             v.alt = None
             v.grad = None
             v.grad_group = None
+        ls = self.loss_scale
+        if ls is not None and ls['n_aux'] and self.is_train:
+            # the moving statistics as they are before this forward rewrites them: a step the guard skips puts them back (_update_body)
+            hip.call('sn_aux_shadow', ls['table'], ls['n_aux'], ls['shadow'], 0, None, hip.stream())
         for s in self.steps:
             s.forward()
         self.outputs = [self.as_f32(self.vals[(id(n), i)]) for n, i in self.sym._heads]
@@ -1017,6 +1022,8 @@ class Executor(object):
             if v is not None and not float(v) > 0.0:
                 raise ValueError('%s must be None or > 0, got %r' % (name, v))
         self._graph_up = None
+        if self.loss_scale is not None:
+            skip_nonfinite = True                  # (dynamic loss scaling implies it: set_loss_scale)
         if clip_gradient is None and clip_global_norm is None and not skip_nonfinite:
             self.guard = None
             return
@@ -1026,9 +1033,80 @@ class Executor(object):
                       'state': self.zeros((8,), torch.float64),
                       'ws': self.empty((max(int(hip.query('sn_grad_guard_workspace_bytes', n, 0)), 256),), torch.uint8)}
 
+    @staticmethod
+    def check_loss_scale(init_scale, growth_interval, growth_factor, backoff_factor, min_scale, max_scale):
+        """ValueError unless these are values set_loss_scale (and sn_grad_guard_scaled) takes"""
+        def pow2(v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                return False
+            v = float(v)
+            return v > 0.0 and np.isfinite(v) and np.frexp(v)[0] == 0.5
+        for name, v in (('init_scale', init_scale), ('growth_factor', growth_factor), ('backoff_factor', backoff_factor),
+                        ('min_scale', min_scale), ('max_scale', max_scale)):
+            if not pow2(v):
+                raise ValueError('loss scale: %s must be a positive power of two, got %r' % (name, v))
+        if isinstance(growth_interval, bool) or not isinstance(growth_interval, (int, np.integer)) or growth_interval < 0:
+            raise ValueError('loss scale: growth_interval must be an int >= 0, got %r' % (growth_interval,))
+        if growth_factor < 1.0 or backoff_factor > 1.0:
+            raise ValueError('loss scale: growth_factor must be >= 1 and backoff_factor <= 1, got %r and %r'
+                             % (growth_factor, backoff_factor))
+        if not 2.0 ** -126 <= min_scale <= init_scale <= max_scale <= 2.0 ** 127:      # (the loss kernels read the scale as a float)
+            raise ValueError('loss scale: need 2^-126 <= min_scale <= init_scale <= max_scale <= 2^127, got %r, %r, %r'
+                             % (min_scale, init_scale, max_scale))
+
+    def set_loss_scale(self, init_scale, growth_interval=2000, growth_factor=2.0, backoff_factor=0.5, min_scale=1.0,
+                       max_scale=2.0 ** 24, restore_aux=True):
+        """Dynamic loss scaling (DESIGN.md "Dynamic loss scaling"): the loss scale is a double in device memory instead of a launch
+        argument.  The loss-gradient kernels of the forward/backward read it (sn_softmax_output_bwd_scaled, sn_fill_scaled_f32: the
+        graph's grad_scale attributes times the scale), sn_grad_guard_scaled judges the gradients they produced -- a non-finite step
+        is skipped (the guard is turned on with skip_nonfinite if it is off; its clipping thresholds are then in TRUE units) --,
+        hands 1 / scale to the guarded update inside the clipping coefficient and moves the scale: times backoff_factor after a
+        skipped step, times growth_factor after growth_interval clean ones (0: never), within [min_scale, max_scale].  restore_aux:
+        the BatchNorm moving statistics the training forward rewrites are saved before it and put back after a skipped step, so
+        that such a step changes nothing at all.  Everything runs inside the two captured graphs, which are both dropped here and
+        captured again; learning rate and weight decay are the true ones.  set_loss_scale(None) turns it off."""
+        if init_scale is None:
+            if self.loss_scale is not None:
+                self.loss_scale = None
+                self._graph_fb = self._graph_up = None
+            return
+        Executor.check_loss_scale(init_scale, growth_interval, growth_factor, backoff_factor, min_scale, max_scale)
+        if self.guard is None:
+            self.set_grad_guard(skip_nonfinite=True)
+        elif not self.guard['skip_nonfinite']:
+            self.guard['skip_nonfinite'] = 1
+        self._graph_fb = self._graph_up = None
+        state = self.zeros((8,), torch.float64)
+        state[0] = float(init_scale)
+        # the vectors a training forward writes besides its outputs: the moving statistics of every batch-statistics BatchNorm
+        aux, seen = [], set()
+        if restore_aux:
+            for st in self.steps:
+                if getattr(st, 'mean', None) is None or getattr(st, 'global_stats', True) or st.is_stem or st.folded_into is not None:
+                    continue
+                for t in (st.mean, st.var):
+                    if t.data_ptr() not in seen:
+                        seen.add(t.data_ptr())
+                        aux.append(t)
+        rec = np.zeros(len(aux), dtype=np.dtype([('ptr', '<u8'), ('off', '<i4'), ('n', '<i4')]))
+        assert rec.dtype.itemsize == 16
+        off = 0
+        for k, t in enumerate(aux):
+            rec[k] = (t.data_ptr(), off, t.numel())
+            off += t.numel()
+        self.loss_scale = {'growth_interval': int(growth_interval), 'growth_factor': float(growth_factor),
+                           'backoff_factor': float(backoff_factor), 'min_scale': float(min_scale), 'max_scale': float(max_scale),
+                           'restore_aux': bool(restore_aux), 'state': state, 'n_aux': len(aux), 'aux': aux,
+                           'table': torch.from_numpy(rec.view(np.uint8).copy()).to(self.device) if len(aux) else None,
+                           'shadow': self.zeros((max(off, 8),), F32)}
+
     def _update_body(self, lr=None, wd=None, momentum=None, rescale_grad=None):
-        g = self.guard
-        if g is not None:
+        g, ls = self.guard, self.loss_scale
+        if ls is not None:
+            hip.call('sn_grad_guard_scaled', self.arena_grad, self.arena_grad.numel(), self.hyper, g['clip_global_norm'], 0,
+                     ls['growth_interval'], ls['growth_factor'], ls['backoff_factor'], ls['min_scale'], ls['max_scale'], g['ws'],
+                     g['state'], ls['state'], hip.stream())
+        elif g is not None:
             hip.call('sn_grad_guard', self.arena_grad, self.arena_grad.numel(), self.hyper, g['clip_global_norm'], g['skip_nonfinite'],
                      0, g['ws'], g['state'], hip.stream())
         for (lr_mult, wd_mult, _half), a, b in self.groups:
@@ -1039,6 +1117,8 @@ class Executor(object):
                 continue
             hip.call('sn_sgd_mom_update_dev', self.arena_master[a:], self.arena_grad[a:], self.arena_mom[a:], self.arena_w16[a:],
                      b - a, self.hyper, float(lr_mult), float(wd_mult), hip.stream())
+        if ls is not None and ls['n_aux']:
+            hip.call('sn_aux_shadow', ls['table'], ls['n_aux'], ls['shadow'], 1, g['state'], hip.stream())
         self.refresh_compute_copies(only_trainable=True)
 
     def update(self, lr, wd, momentum, rescale_grad=1.0):

@@ -1122,8 +1122,13 @@ class SoftmaxOutputStep(Step):
         scale = self.grad_scale
         if self.norm == 'batch':
             scale = scale / float(self.outer)
-        hip.call('sn_softmax_output_bwd', self.y.t, ex.as_f32(self.label), g, self.outer, self.K, self.inner, self.ignore,
-                 1 if self.use_ignore else 0, scale, 1 if self.norm == 'valid' else 0, self.cnt, hip.stream())
+        if ex.loss_scale is not None:      # dynamic loss scaling: the kernel multiplies with the scale the device holds
+            hip.call('sn_softmax_output_bwd_scaled', self.y.t, ex.as_f32(self.label), g, self.outer, self.K, self.inner, self.ignore,
+                     1 if self.use_ignore else 0, scale, 1 if self.norm == 'valid' else 0, self.cnt, ex.loss_scale['state'],
+                     hip.stream())
+        else:
+            hip.call('sn_softmax_output_bwd', self.y.t, ex.as_f32(self.label), g, self.outer, self.K, self.inner, self.ignore,
+                     1 if self.use_ignore else 0, scale, 1 if self.norm == 'valid' else 0, self.cnt, hip.stream())
         ex.add_grad(self.x, g, 'f32')
 
 
@@ -1191,7 +1196,10 @@ class MakeLossStep(Step):
         if not self.x.needs_grad:
             return
         g = self.ex.empty(self.x.shape, F32)
-        hip.call('sn_ew_f32', None, None, g, g.numel(), 4, self.grad_scale, hip.stream())
+        if self.ex.loss_scale is not None:
+            hip.call('sn_fill_scaled_f32', g, g.numel(), self.grad_scale, self.ex.loss_scale['state'], hip.stream())
+        else:
+            hip.call('sn_ew_f32', None, None, g, g.numel(), 4, self.grad_scale, hip.stream())
         self.ex.add_grad(self.x, g, 'f32')
 
 

@@ -248,7 +248,11 @@ class Module(object):
         arg, aux = self.get_params()
         save_checkpoint(prefix, epoch, self.symbol, arg, aux)
         if save_optimizer_states:
-            torch.save({'momentum': self.exe.arena_mom.cpu(), 'num_update': self.exe.num_update}, '%s-%04d.states' % (prefix, epoch))
+            states = {'momentum': self.exe.arena_mom.cpu(), 'num_update': self.exe.num_update}
+            if self.exe.loss_scale is not None:            # dynamic loss scaling: a resumed run goes on at this scale
+                ls = self.exe.loss_scale['state'].cpu().tolist()
+                states['loss_scale'], states['clean'] = float(ls[0]), int(ls[2])
+            torch.save(states, '%s-%04d.states' % (prefix, epoch))
 
     # ---- optimizer (mx 'sgd' with multi_precision; lib/train_utils/utils.py:26-33)
     def init_optimizer(self, kvstore='local', optimizer='sgd', optimizer_params=(('learning_rate', 0.01),), force_init=False):
@@ -256,6 +260,7 @@ class Module(object):
             raise NotImplementedError('optimizer %r (the reference trains with sgd)' % (optimizer,))
         op = dict(optimizer_params)
         guard = self._guard_options(op)
+        guard['loss_scale'] = self._loss_scale_options(op.get('dynamic_loss_scale'))
         self.opt = {'lr': float(op.get('learning_rate', 0.01)), 'wd': float(op.get('wd', 0.0)),
                     'momentum': float(op.get('momentum', 0.0)), 'rescale_grad': float(op.get('rescale_grad', 1.0)),
                     'lr_scheduler': op.get('lr_scheduler')}
@@ -264,6 +269,7 @@ class Module(object):
             self.opt['lr_scheduler'].base_lr = self.opt['lr']
         self.optimizer_initialized = True
         self._guard_host = None
+        self._loss_scale_resume = None
         for ex in getattr(self, '_exes', {}).values():
             self._guard_exe(ex)
 
@@ -292,13 +298,88 @@ class Module(object):
         out['guard'] = out['clip_gradient'] is not None or out['clip_global_norm'] is not None or out['skip_nonfinite']
         return out
 
+    # ---- dynamic loss scaling (Executor.set_loss_scale): optimizer parameter dynamic_loss_scale = None / False, True, or a dict of
+    # set_loss_scale's arguments.  Learning rate and weight decay are then the TRUE ones (nothing folded), clip_gradient and
+    # clip_global_norm are in true units, and grad_guard_state()['norm'] is the true norm.
+    _LOSS_SCALE_DEFAULTS = (('init_scale', 2.0 ** 16), ('growth_interval', 2000), ('growth_factor', 2.0), ('backoff_factor', 0.5),
+                            ('min_scale', 1.0), ('max_scale', 2.0 ** 24), ('restore_aux', True))
+
+    @classmethod
+    def _loss_scale_options(cls, v):
+        if v is None or v is False:
+            return None
+        if v is True:
+            v = {}
+        if not isinstance(v, dict):
+            raise ValueError('optimizer parameter dynamic_loss_scale must be None, a bool or a dict, got %r' % (v,))
+        out = dict(cls._LOSS_SCALE_DEFAULTS)
+        unknown = sorted(set(v) - set(out))
+        if unknown:
+            raise ValueError('optimizer parameter dynamic_loss_scale: unknown keys %s (known: %s)' % (unknown, sorted(out)))
+        out.update(v)
+
+        from ..engine.executor import Executor
+        Executor.check_loss_scale(**{k: out[k] for k in out if k != 'restore_aux'})
+        for key in ('init_scale', 'growth_factor', 'backoff_factor', 'min_scale', 'max_scale'):
+            out[key] = float(out[key])
+        out['growth_interval'] = int(out['growth_interval'])
+        if not isinstance(out['restore_aux'], (bool, np.bool_)):
+            raise ValueError('dynamic_loss_scale: restore_aux must be a bool, got %r' % (out['restore_aux'],))
+        out['restore_aux'] = bool(out['restore_aux'])
+        return out
+
     def _guard_exe(self, ex):
-        """the optimizer's guard options -> a training executor (at init_optimizer for the bound ones, at bind for later ones)"""
+        """the optimizer's guard and loss-scale options -> a training executor (at init_optimizer for the bound ones, at bind for later
+        ones)"""
         opt = getattr(self, 'opt', None)
         if opt is None or not ex.for_training:
             return
-        if opt['guard'] or ex.guard is not None:
-            ex.set_grad_guard(opt['clip_gradient'], opt['clip_global_norm'], opt['skip_nonfinite'])
+        ls = opt.get('loss_scale')
+        if ls is None and ex.loss_scale is not None:
+            ex.set_loss_scale(None)                     # (first: while it is on, the guard cannot be turned off)
+        if opt['guard'] or ex.guard is not None or ls is not None:
+            ex.set_grad_guard(opt['clip_gradient'], opt['clip_global_norm'], opt['skip_nonfinite'] or ls is not None)
+        if ls is not None:
+            ex.set_loss_scale(**ls)
+            resume = getattr(self, '_loss_scale_resume', None)
+            if resume is not None:                      # load_optimizer_states: go on at the checkpoint's scale
+                ex.loss_scale['state'][0] = float(resume[0])
+                ex.loss_scale['state'][2] = float(resume[1])
+
+    _LOSS_SCALE_KEYS = ('scale', 'scale_used', 'clean', 'growths', 'backoffs', 'held_max', 'held_min')
+
+    @classmethod
+    def _loss_scale_dict(cls, s):
+        return dict(zip(cls._LOSS_SCALE_KEYS, (float(s[0]), float(s[1]), int(s[2]), int(s[3]), int(s[4]), int(s[5]), int(s[6]))))
+
+    def loss_scale_state(self, wait=True):
+        """The dynamic loss scaler's device state as a dict -- scale (what the next forward multiplies with), scale_used (what the
+        gradients of the last step carried), clean steps since the scale changed, growths, backoffs, held_max, held_min -- or None
+        when it is off.  wait as in grad_guard_state: True reads the device now, False returns the newest landed snapshot."""
+        ls = self.exe.loss_scale if getattr(self, 'exe', None) is not None else None
+        if ls is None:
+            return None
+        if wait:
+            return self._loss_scale_dict(ls['state'].cpu().tolist())
+        s = self._guard_landed()
+        return self._loss_scale_dict(s[8:]) if s is not None and len(s) >= 16 else None
+
+    def load_optimizer_states(self, fname):
+        """A `.states` file of save_checkpoint(save_optimizer_states=True): the momentum arena and the update count; with dynamic
+        loss scaling on, and a file that holds them, the loss scale and its clean-step count too (a file without them: the scale
+        stays where it is)."""
+        st = torch.load(fname, map_location='cpu')
+        self.exe.arena_mom.copy_(st['momentum'].to(self.exe.arena_mom.device))
+        self.exe.num_update = int(st['num_update'])
+        if 'loss_scale' in st and self.opt.get('loss_scale') is not None:
+            scale = float(st['loss_scale'])
+            if not (scale > 0.0 and np.isfinite(scale) and np.frexp(scale)[0] == 0.5):
+                raise ValueError('%s: loss_scale %r is not a positive power of two' % (fname, st['loss_scale']))
+            self._loss_scale_resume = (scale, float(st.get('clean', 0)))
+            for ex in self._exes.values():
+                if ex.loss_scale is not None:
+                    ex.loss_scale['state'][0] = scale
+                    ex.loss_scale['state'][2] = self._loss_scale_resume[1]
 
     _GUARD_KEYS = ('norm', 'coef', 'skipped_last', 'nonfinite', 'steps', 'skipped', 'consecutive', 'sumsq')
 
@@ -308,20 +389,26 @@ class Module(object):
 
     def grad_guard_state(self, wait=True):
         """The guard's device state as a dict (norm and sumsq in the arena's units: with TRAIN.fp16 the gradients carry the static
-        loss scale), None when the guard is off.  wait=True reads the device now (waits for the steps enqueued so far);
+        loss scale; with dynamic loss scaling on -- loss_scale_state -- norm is in TRUE units, divided by the scale the gradients
+        carried, and only sumsq stays in the arena's), None when the guard is off.  wait=True reads the device now (waits for the steps enqueued so far);
         wait=False returns the newest snapshot that has already landed on the host -- one or two steps old -- or None before the first."""
         g = self.exe.guard if getattr(self, 'exe', None) is not None else None
         if g is None:
             return None
         if wait:
             return self._guard_dict(g['state'].cpu().tolist())
+        s = self._guard_landed()
+        return self._guard_dict(s) if s is not None else None
+
+    def _guard_landed(self):
+        """the newest snapshot that has landed on the host (looks only: update() does the inspecting), or None"""
         host = getattr(self, '_guard_host', None)
         if host is None:
             return None
         landed = [s['host'].tolist() for s in host['slots'] if s['event'] is not None and s['event'].query()]
         if host['last'] is not None:
             landed.append(host['last'])
-        return self._guard_dict(max(landed, key=lambda s: s[4])) if landed else None      # (looks only: update() does the inspecting)
+        return max(landed, key=lambda s: s[4]) if landed else None
 
     def _guard_snapshot(self):
         """After a guarded step has been enqueued: its 64 bytes of state -> pinned host memory without waiting (a device copy on the
@@ -329,11 +416,17 @@ class Module(object):
         _snapshot_for_metric does for the outputs); then whatever EARLIER snapshot has landed is inspected: a skipped step is logged
         once, max_consecutive_skips skipped steps in a row raise FloatingPointError.  Never waits for the device."""
         g = self.exe.guard
+        ls = self.exe.loss_scale
+        nd_ = 16 if ls is not None else 8              # with dynamic loss scaling the scaler's eight doubles ride behind the guard's
         host = getattr(self, '_guard_host', None)
+        if host is not None and host['slots'][0]['host'].numel() != nd_:
+            host = None
         if host is None:
             host = self._guard_host = {
                 'stream': torch.cuda.Stream(device=self._device), 'k': 0, 'last': None, 'skipped': 0, 'steps': 0,
-                'slots': [{'dev': torch.zeros_like(g['state']), 'host': torch.zeros(8, dtype=torch.float64, pin_memory=True),
+                'growths': 0, 'backoffs': 0,
+                'slots': [{'dev': torch.zeros(nd_, dtype=torch.float64, device=g['state'].device),
+                           'host': torch.zeros(nd_, dtype=torch.float64, pin_memory=True),
                            'event': None, 'fresh': False} for _ in range(2)]}
         self._guard_poll(host)                                 # (before the older slot is reused)
         slot = host['slots'][host['k'] & 1]
@@ -341,7 +434,11 @@ class Module(object):
         main = torch.cuda.current_stream(self._device)
         if slot['event'] is not None:
             main.wait_event(slot['event'])                     # device-side: the slot's previous copy out has read slot['dev']
-        slot['dev'].copy_(g['state'])
+        if ls is not None:
+            slot['dev'][:8].copy_(g['state'])
+            slot['dev'][8:].copy_(ls['state'])
+        else:
+            slot['dev'].copy_(g['state'])
         cloned = torch.cuda.Event()
         cloned.record(main)
         side = host['stream']
@@ -366,10 +463,26 @@ class Module(object):
                                         '(%d skipped of %d steps, %d in a row)', int(s[4]), int(s[3]), s[0], int(s[5]), int(s[4]), int(s[6]))
                 else:
                     self.logger.warning('gradient guard: %d of %d steps skipped so far', int(s[5]), int(s[4]))
+            if len(s) >= 16:
+                self._loss_scale_log(host, s)
             limit = self.opt.get('max_consecutive_skips')
             if limit is not None and s[6] >= limit:
                 raise FloatingPointError('gradient guard: %d consecutive steps skipped for non-finite gradients (step %d, %d non-finite '
                                          'elements in the last one); max_consecutive_skips = %d' % (int(s[6]), int(s[4]), int(s[3]), limit))
+
+    def _loss_scale_log(self, host, s):
+        """one landed snapshot (guard's eight doubles, then the scaler's): a back-off is a warning, a growth an info line, once each"""
+        scale, used, growths, backoffs = s[8], s[9], s[11], s[12]
+        if backoffs > host['backoffs']:
+            if s[2] and backoffs == host['backoffs'] + 1:
+                self.logger.warning('loss scale: step %d skipped, %d non-finite gradient elements: scale %g -> %g (%d back-offs)',
+                                    int(s[4]), int(s[3]), used, scale, int(backoffs))
+            else:
+                self.logger.warning('loss scale: %d back-offs so far (step %d), scale now %g', int(backoffs), int(s[4]), scale)
+            host['backoffs'] = backoffs
+        if growths > host['growths']:
+            self.logger.info('loss scale: step %d, scale %g -> %g (%d growths)', int(s[4]), used, scale, int(growths))
+            host['growths'] = growths
 
     # ---- compute
     def _adopt_iterator(self, train_data):

@@ -112,6 +112,8 @@ class mobilenetv2_e2e(Symbol):
         rpn_cls_score_reshape = mx.sym.Reshape(data=rpn_cls_score, shape=(0, 2, -1, 0), name='rpn_cls_score_reshape')
         if is_train:
             grad_scale = float(cfg.TRAIN.scale) if cfg.TRAIN.fp16 else 1.0
+            if getattr(cfg.TRAIN, 'DYNAMIC_SCALE', False):      # the device holds the scale (Executor.set_loss_scale): not twice
+                grad_scale = 1.0
             B = cfg.TRAIN.BATCH_IMAGES
             rpn_cls_prob = mx.sym.SoftmaxOutput(data=rpn_cls_score_reshape, label=rpn_label, multi_output=True,
                                                 normalization='valid', use_ignore=True, ignore_label=-1, name='rpn_cls_prob',

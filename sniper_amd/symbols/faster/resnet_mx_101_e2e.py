@@ -124,6 +124,10 @@ class resnet_mx_101_e2e(Symbol):
         return self.get_rpn(cat, num_anchors)
 
     def _scale(self, cfg):
+        # TRAIN.DYNAMIC_SCALE: the loss scale lives on the device (Executor.set_loss_scale) and the loss kernels multiply with it --
+        # the attributes must not carry a scale of their own, or it would be applied twice
+        if getattr(cfg.TRAIN, 'DYNAMIC_SCALE', False):
+            return 1.0
         return float(cfg.TRAIN.scale) if cfg.TRAIN.fp16 else 1.0
 
     def _rpn_losses(self, cfg, cls_reshape, bbox_pred, label, target, weight):

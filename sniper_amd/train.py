@@ -18,6 +18,23 @@ def fixed_param_names(cfg, sym):
     return out
 
 
+def dynamic_loss_scale(cfg):
+    """TRAIN.DYNAMIC_SCALE (True, or a dict of Executor.set_loss_scale's arguments) and TRAIN.DYNAMIC_SCALE_INIT -- two keys the
+    reference's configs do not have, absent means off -- -> the optimizer parameter dynamic_loss_scale (None: off).  Without an
+    initial scale the run starts at the power of two nearest to the static TRAIN.scale in log2 (100 -> 128)."""
+    tr = cfg.TRAIN
+    ds = getattr(tr, 'DYNAMIC_SCALE', None)
+    if ds is None or ds is False:
+        return None
+    opt = dict(ds) if isinstance(ds, dict) else {}
+    if 'init_scale' not in opt:
+        init = getattr(tr, 'DYNAMIC_SCALE_INIT', None)
+        if init is None:
+            init = 2.0 ** int(np.floor(np.log2(float(tr.scale)) + 0.5))
+        opt['init_scale'] = init
+    return opt
+
+
 def optimizer_params(cfg, lr_scheduler=None):
     """lib/train_utils/utils.py:13-42: fp16 folds the static loss scale into lr and wd."""
     tr = cfg.TRAIN
@@ -25,6 +42,12 @@ def optimizer_params(cfg, lr_scheduler=None):
     # arena holds gradients multiplied by the static loss scale: the two thresholds are in those units.
     guard = {'clip_gradient': getattr(tr, 'CLIP_GRADIENT', None), 'clip_global_norm': getattr(tr, 'CLIP_GLOBAL_NORM', None),
              'skip_nonfinite': bool(getattr(tr, 'SKIP_NONFINITE', False))}
+    dyn = dynamic_loss_scale(cfg)
+    if dyn is not None:
+        # the scale lives on the device and the update divides it out again: lr and wd are the true ones, nothing is folded, and
+        # the guard's two thresholds are in true units
+        return dict({'momentum': tr.momentum, 'wd': tr.wd, 'learning_rate': tr.lr, 'rescale_grad': 1.0, 'multi_precision': True,
+                     'lr_scheduler': lr_scheduler, 'dynamic_loss_scale': dyn}, **guard)
     if tr.fp16:
         return dict({'momentum': tr.momentum, 'wd': tr.wd * tr.scale, 'learning_rate': tr.lr / tr.scale, 'rescale_grad': 1.0,
                      'multi_precision': True, 'lr_scheduler': lr_scheduler}, **guard)
@@ -44,12 +67,18 @@ class Trainer(object):
     largest loss carry the R-CNN losses, on the device, inside the replayed step (None keeps the config's two keys).
     `clip_gradient`, `clip_global_norm`, `skip_nonfinite` turn the gradient guard of the optimizer pass on (TRAIN.CLIP_GRADIENT,
     TRAIN.CLIP_GLOBAL_NORM, TRAIN.SKIP_NONFINITE; Module.init_optimizer): a step whose gradients hold inf / NaN is skipped, the rest is
-    clipped -- thresholds in the arena's units, i.e. times TRAIN.scale with fp16."""
+    clipped -- thresholds in the arena's units, i.e. times TRAIN.scale with fp16.
+    `dynamic_loss_scale` (True, or a dict of Executor.set_loss_scale's arguments; TRAIN.DYNAMIC_SCALE) replaces the static loss scale
+    by one the device keeps: halved when a step overflows -- that step is skipped and leaves the BatchNorm moving statistics as they
+    were --, doubled after growth_interval clean steps; lr, wd and the guard's thresholds are then in true units."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
-                 fix_bn=False, fixed_params=None, ohem=None, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False):
+                 fix_bn=False, fixed_params=None, ohem=None, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False,
+                 dynamic_loss_scale=None):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
+        if dynamic_loss_scale is not None and dynamic_loss_scale is not False:
+            cfg.TRAIN.DYNAMIC_SCALE = dynamic_loss_scale       # (before the symbol is built: its grad_scale attributes become 1 x)
         if clip_gradient is not None:
             cfg.TRAIN.CLIP_GRADIENT = clip_gradient
         if clip_global_norm is not None:
