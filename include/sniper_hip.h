@@ -979,6 +979,47 @@ int sn_render_dets(int form, const void *src, const int32_t *hw, const int64_t *
                    int n_masks, int M, float binary_thresh, int mask_alpha, int line_width, float mean0, float mean1, float mean2,
                    uint8_t *out, sn_stream_t stream);
 
+/* PNG encoding of a batch of pictures: the row filters, and a deflate coder of many byte buffers that is public
+ * on its own.  Integer arithmetic, exact bytes, the same every run; no global atomics, no host read-back inside any call.
+ * Deflate: S streams pooled in data behind offsets (S+1) i64 -> one zlib stream (RFC 1950: 78 01, deflate blocks, big-endian
+ *   Adler-32) per input stream.  A stream is cut into blocks of B = 32768 bytes (an empty stream has one empty block); one workgroup
+ *   codes one block.  Tokens, inside a block: every maximal run of equal bytes [s, e) is a literal at s, then its remaining e - s - 1
+ *   bytes in pieces of 258 from the left -- a piece of >= 3 bytes is a match (length, distance 1), a piece of 1 or 2 bytes that many
+ *   literals.  Per block a dynamic Huffman code (BTYPE 2), lengths limited to 15 bits (code lengths: 7), complete, ties by symbol
+ *   index; all 286 literal/length lengths and one distance length (1, or 0 in a block without matches) are sent without repeat
+ *   symbols.  A dynamic block that is not the last of its stream is followed by an empty stored block (byte alignment); a block whose
+ *   coded bytes would exceed len + 5 is stored (BTYPE 0).  For a stream of n bytes in nb = ceil(n / B) blocks the output is at most
+ *   sn_deflate_bound(n) = n + 5 * (nb + 1) + 6 bytes.
+ *   The offsets are given twice, as everywhere here: on the device (what the kernels read) and as the HOST array they were uploaded
+ *   from (h_offsets, what the entry point checks).  The calls, in order:
+ *     sn_deflate_plan   blk_first (S+1) i32 = the running block count; n_blocks = blk_first[S] is known to the host from h_offsets.
+ *     sn_deflate_code   per block: blk_code (n_blocks, code_words) u32 -- the code, the header bits, the Adler-32 partial sums -- and
+ *                       blk_size (n_blocks) i64 = the block's bytes in the output, the 2 header bytes of a stream's first block and the
+ *                       4 Adler-32 bytes of its last one included.
+ *     (caller)          blk_pos (n_blocks) i64 = the exclusive prefix sum of blk_size: the streams come out compact, stream s at
+ *                       blk_pos[blk_first[s]].
+ *     sn_deflate_write  the bytes; out has room for `capacity` bytes and nothing is written at or past out + capacity.
+ *   Refused before any launch, by a message that names the function and the condition: NULL pointers; S outside 1 .. 65535; offsets
+ *   that do not start at 0, are not ascending or do not end at `total`; n_blocks other than the offsets give; a capacity below the sum
+ *   of sn_deflate_bound over the streams.
+ * sn_deflate_limits: h_out6 (HOST) = {B, threads per workgroup, the largest S, code_words, LDS bytes of the code kernel, LDS bytes of
+ *   the write kernel (dynamic)}.
+ * sn_png_filter: pictures as sn_render_dets writes them (uint8 HWC RGB, picture i at byte 3 * pix_off[i], hw[i] = (h, w)) -> the
+ *   filtered stream of picture i at out + stream_off[i]: per row one filter-type byte and 3 * w bytes.  All five filters of the PNG
+ *   specification (bpp = 3; the row above the first and the pixels left of the first are zero; Average floors the 9-bit sum; Paeth
+ *   breaks ties a, b, c); the filter with the smallest sum of min(v, 256 - v) over the row's filtered bytes is kept, ties to the
+ *   lowest type.  h_hw: the sizes on the HOST; total_pixels and total_stream = sum of h * (3 * w + 1) must match them. */
+int sn_deflate_limits(int32_t *h_out6);
+long sn_deflate_bound(long n);
+int sn_deflate_plan(const int64_t *offsets, const int64_t *h_offsets, long S, long total, int32_t *blk_first, sn_stream_t stream);
+int sn_deflate_code(const uint8_t *data, const int64_t *offsets, const int64_t *h_offsets, long S, long total,
+                    const int32_t *blk_first, long n_blocks, uint32_t *blk_code, int64_t *blk_size, sn_stream_t stream);
+int sn_deflate_write(const uint8_t *data, const int64_t *offsets, const int64_t *h_offsets, long S, long total,
+                     const int32_t *blk_first, long n_blocks, const uint32_t *blk_code, const int64_t *blk_pos, uint8_t *out,
+                     long capacity, sn_stream_t stream);
+int sn_png_filter(const uint8_t *pix, const int32_t *hw, const int32_t *h_hw, const int64_t *pix_off, const int64_t *stream_off, int I,
+                  long total_pixels, long total_stream, uint8_t *out, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

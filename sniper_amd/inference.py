@@ -489,11 +489,17 @@ class Tester(object):
             # reference hard-codes '.pdf' here (:219-220), vis_ext is honoured instead
             from .visualization import render_results
             render_results(self.roidb, all_boxes, self.class_names, self._vis_dir(vis_path, cache_name),
-                           threshold=0.5, vis_ext=vis_ext, names=[vis_name] * self.num_images if vis_name else None)
+                           threshold=0.5, vis_ext=vis_ext, names=[vis_name] * self.num_images if vis_name else None,
+                           encoder=self._vis_encoder())
         return all_boxes
 
     def _vis_dir(self, vis_path, cache_name):
         return vis_path or os.path.join(getattr(self.cfg.TEST, 'VISUALIZATION_PATH', os.path.join('debug', 'visualization')), cache_name)
+
+    def _vis_encoder(self):
+        """cfg.TEST.VIS_ENCODER: 'pil' (the default) or 'device' -- who encodes the '.png' files of vis=True (visualization._save_all)"""
+        t = self.cfg.TEST
+        return t.get('VIS_ENCODER', 'pil') if hasattr(t, 'get') else getattr(t, 'VIS_ENCODER', 'pil')
 
     def _vis_names(self):
         return list(self.class_names) if self.class_names is not None else \
@@ -502,7 +508,7 @@ class Tester(object):
     def _vis_chips(self, data, dets_of, file_of, class_names, out_dir, vis_ext):
         """The chips of one batch drawn from its `data` tensor while it is still in HBM, one device call (visualization.render_batch):
         dets_of(i) = the per-class rows of chip i, scale im_info[i, 2], the reference's transform_im means (:24)."""
-        from .visualization import _save, render_batch
+        from .visualization import _save_all, render_batch
         if not os.path.isdir(out_dir):
             os.makedirs(out_dir)
         x = data['data']
@@ -511,8 +517,7 @@ class Tester(object):
         B = int(x.shape[0])
         pics = render_batch(x.float() if isinstance(x, torch.Tensor) else np.asarray(x, np.float32), [dets_of(i) for i in range(B)], class_names, [float(im_info[i, 2]) for i in range(B)],
                             np.asarray(self.cfg.network.PIXEL_MEANS, np.float32)[[2, 1, 0]], 0.5)
-        for i, pic in enumerate(pics):
-            _save(pic.cpu().numpy() if isinstance(pic, torch.Tensor) else pic, os.path.join(out_dir, file_of(i) + vis_ext))
+        _save_all(pics, [os.path.join(out_dir, file_of(i) + vis_ext) for i in range(len(pics))], self._vis_encoder())
 
     def _aggregate_host(self, scale_cls_dets):
         all_boxes = [[[] for _ in range(self.num_images)] for _ in range(self.num_classes)]

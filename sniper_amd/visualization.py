@@ -246,13 +246,36 @@ def _save(arr, path):
     Image.fromarray(np.ascontiguousarray(arr)).save(path)
 
 
+ENCODERS = ('pil', 'device')
+
+
+def _check_encoder(encoder):
+    if encoder not in ENCODERS:
+        raise ValueError("encoder=%r: 'pil' (the default) or 'device'" % (encoder,))
+
+
+def _save_all(pics, paths, encoder='pil'):
+    """pics[i] -> paths[i].  encoder='device': a '.png' path (any letter case) is encoded on the device (sniper_amd/png.py), device
+    tensors without their raw bytes coming to the host; every other file, and every file of encoder='pil', is written by PIL."""
+    import torch
+    _check_encoder(encoder)
+    dev = [k for k, path in enumerate(paths) if encoder == 'device' and os.path.splitext(path)[1].lower() == '.png']
+    if dev:
+        from .png import write_png
+        write_png([paths[k] for k in dev], [pics[k] for k in dev])
+    for k in sorted(set(range(len(paths))) - set(dev)):
+        _save(pics[k].cpu().numpy() if isinstance(pics[k], torch.Tensor) else pics[k], paths[k])
+
+
 def visualize_dets(im, dets, scale, pixel_means, class_names, threshold=0.5, save_path='debug.png', transform=True, dpi=80, masks=None,
-                   binary_thresh=0.4):
+                   binary_thresh=0.4, encoder='pil'):
     """The reference's entry point, signature and meaning (lib/data_utils/visualization.py:21-57): transform=True takes the (3, h, w)
     network input and adds pixel_means[[2, 1, 0]] back (transform_im; clamped here); transform=False an (h, w, 3) uint8 RGB image.
     masks[j]: (n, M, M) maps aligned with dets[j].  `dpi` is accepted and unused: a pixel of the image is a pixel of the file.  The
-    file's extension decides its format (PIL).  -> the (h, w, 3) uint8 picture."""
+    file's extension decides its format (PIL); encoder='device' writes a '.png' file with this project's encoder (sniper_amd/png.py).
+    -> the (h, w, 3) uint8 picture."""
     import torch
+    _check_encoder(encoder)
     if transform:
         t = im if isinstance(im, torch.Tensor) else torch.as_tensor(np.asarray(im, np.float32))
         pic = render_batch(t[None], [dets], class_names, scale, np.asarray(pixel_means, np.float32)[[2, 1, 0]], threshold,
@@ -260,9 +283,11 @@ def visualize_dets(im, dets, scale, pixel_means, class_names, threshold=0.5, sav
     else:
         pic = render_batch([im if isinstance(im, torch.Tensor) else np.ascontiguousarray(im, np.uint8)], [dets], class_names, scale, None,
                            threshold, [masks] if masks is not None else None, binary_thresh)[0]
+    if save_path and encoder == 'device':
+        _save_all([pic], [save_path], encoder)
     if isinstance(pic, torch.Tensor):
         pic = pic.cpu().numpy()
-    if save_path:
+    if save_path and encoder != 'device':
         _save(pic, save_path)
     return pic
 
@@ -274,11 +299,13 @@ def _load_rgb(entry):
 
 
 def render_results(roidb, all_boxes, class_names, out_dir, all_masks=None, threshold=0.5, vis_ext='.png', names=None,
-                   binary_thresh=0.4, budget_bytes=256 << 20):
+                   binary_thresh=0.4, budget_bytes=256 << 20, encoder='pil'):
     """A data set's final detections as pictures: image i of roidb (its file `image`, mirrored when `flipped`) with
     all_boxes[j][i] -- and all_masks[j][i], what mask_inference.predict_masks returns -- drawn at scale 1, saved as
     out_dir/{names[i] or i}{vis_ext}.  Images are rendered in batches whose source bytes stay under budget_bytes (one device call
-    each).  -> the paths written, in image order."""
+    each).  encoder='device': '.png' files are encoded on the device, a batch per call, from the rendered pictures where they lie.
+    -> the paths written, in image order."""
+    _check_encoder(encoder)
     if not os.path.isdir(out_dir):
         os.makedirs(out_dir)
     K = len(all_boxes)
@@ -289,10 +316,18 @@ def render_results(roidb, all_boxes, class_names, out_dir, all_masks=None, thres
         ims = [b[1] for b in batch]
         dets = [[[]] + [all_boxes[j][b[0]] for j in range(1, K)] for b in batch]
         masks = [[None] + [all_masks[j][b[0]] for j in range(1, K)] for b in batch] if all_masks is not None else None
-        for b, pic in zip(batch, render_batch(ims, dets, class_names, 1.0, None, threshold, masks, binary_thresh)):
-            path = os.path.join(out_dir, '{}{}'.format(names[b[0]] if names is not None else b[0], vis_ext))
-            _save(pic, path)
-            paths.append(path)
+        if encoder == 'device':
+            import torch
+            from . import hip
+            ims = [torch.as_tensor(im).to(hip.require_gpu()) for im in ims]          # device sources: the pictures stay in HBM
+        pics = render_batch(ims, dets, class_names, 1.0, None, threshold, masks, binary_thresh)
+        out = [os.path.join(out_dir, '{}{}'.format(names[b[0]] if names is not None else b[0], vis_ext)) for b in batch]
+        if encoder == 'device':
+            _save_all(pics, out, encoder)
+        else:
+            for pic, path in zip(pics, out):
+                _save(pic, path)
+        paths.extend(out)
         del batch[:]
 
     for i, entry in enumerate(roidb):
