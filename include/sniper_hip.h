@@ -1020,6 +1020,49 @@ int sn_deflate_write(const uint8_t *data, const int64_t *offsets, const int64_t 
 int sn_png_filter(const uint8_t *pix, const int32_t *hw, const int32_t *h_hw, const int64_t *pix_off, const int64_t *stream_off, int I,
                   long total_pixels, long total_stream, uint8_t *out, sn_stream_t stream);
 
+/* Baseline JPEG decoding of a batch of files: compressed bytes in, (H, W, 3) uint8 BGR pictures out, bit for
+ * bit what libjpeg's slow-integer IDCT with fancy upsampling gives.  Integer arithmetic, the same bytes every run; plain vector stores;
+ * the only atomic is the OR of a non-zero status into its image's word.  The host finds the markers and builds three tables; as
+ * everywhere here each comes twice, on the device (what the kernels read) and as the HOST array it was uploaded from (h_*, what the
+ * entry point checks before any launch).
+ *   img (I, 16) i32: W, H, components (1, or 3 = YCbCr), luma sampling hs, vs (1x1, 2x1 or 2x2; chroma is 1x1), MCU columns, MCU rows,
+ *     blocks per MCU, first segment, segments, first block (in the coefficient buffer), first byte of its planes (16-byte aligned),
+ *     first byte of its stream in `data`, length of its stream, table bits (bit 2c: the DC table of component c, bit 2c + 1: its AC
+ *     table), restart interval in MCUs (0: none).  Images follow one another in segments and blocks without gaps.
+ *   seg (S, 8) i32: image, first byte and end byte of the segment's entropy-coded data inside the image's stream (a segment is a
+ *     restart interval, or the whole scan), first subsequence, subsequences = max(1, ceil(bytes / sub_bytes)); three unused.
+ *   dht (I, 4, 272) u8: the tables DC 0, DC 1, AC 0, AC 1 as a DHT segment holds them (16 counts, then the values), zero where absent.
+ *   qtab (I, 3, 64) u16: the quantisation table of each component in natural (row-major) order.
+ * sn_jpeg_entropy: one workgroup per segment.  phases bit 0: the self-synchronising rounds over subsequences of sub_bytes bytes (lane
+ *   i decodes from the guess "a block starts here", then takes the exit state of the subsequence before it as its entry and decodes
+ *   again only where that entry changed, until a round changes nothing -- at most as many rounds as the segment has subsequences) and
+ *   the exclusive scan of the completed-block counts; rounds (S) i32 gets the rounds each segment took.  phases bit 1: the pass that
+ *   writes the coefficients from the exact entries: coef (n_blocks, 64) i16, blocks in scan order, natural order inside a block, DC as
+ *   differences -- into a buffer the caller has ZEROED.  3 runs both in one launch; 2 needs the state a call with 1 left.
+ *   state (3, n_sub, 2) u32 and counts (2, n_sub) i32 are scratch.  status (I) i32, zeroed by the caller, collects per image:
+ *   1 no code matches / a category too large, 2 a run past coefficient 63, 4 a symbol past the end of its segment, 8 a segment
+ *   with another number of blocks than the header says, 16 a DC value outside int16, 32 samples outside the range in which all
+ *   libjpeg IDCT forms agree, 64 a missing or wrong restart marker.  Nothing is read past a stream or written past a segment's blocks
+ *   whatever the data holds.
+ * sn_jpeg_dc: the running sum of the DC differences per component inside each segment, in place.
+ * sn_jpeg_pixels: dequantise, IDCT into component planes (scratch, plane_bytes >= the sum of 64-byte-aligned 64 * blocks), upsample,
+ *   convert, and write picture i to out_ptrs[i] (device addresses, u64; H * W * 3 bytes each, 4-byte aligned).  MCU padding is never
+ *   written to a picture.
+ * sn_jpeg_limits: h_out8 (HOST) = {default sub_bytes (SNIPER_JPEG_SUB), threads per workgroup, the largest I, the most blocks per MCU,
+ *   LDS bytes of the four decoding tables, fields per image, fields per segment, the smallest sub_bytes}.
+ * Refused before any launch, by a message that names the function and the condition: NULL pointers; I outside 1 .. 65535; sizes,
+ *   samplings, MCU grids, segment counts or offsets that do not follow from one another; a stream or a segment outside `data`; a
+ *   subsequence table other than sub_bytes gives; sub_bytes outside 16 .. 4096; a segment of more than 16384 subsequences (its
+ *   rounds are one workgroup's: such scans are the host's); totals of 2^31 bytes or 2^25 blocks and more. */
+int sn_jpeg_limits(int32_t *h_out8);
+int sn_jpeg_entropy(const uint8_t *data, long total_bytes, const int32_t *img, const int32_t *h_img, int I, const int32_t *seg,
+                    const int32_t *h_seg, int S, const uint8_t *dht, int sub_bytes, long n_sub, long n_blocks, uint32_t *state,
+                    int32_t *counts, int16_t *coef, int32_t *rounds, int32_t *status, int phases, sn_stream_t stream);
+int sn_jpeg_dc(const int32_t *img, const int32_t *h_img, int I, const int32_t *seg, const int32_t *h_seg, int S, long n_blocks,
+               int16_t *coef, int32_t *status, sn_stream_t stream);
+int sn_jpeg_pixels(const int32_t *img, const int32_t *h_img, int I, const uint16_t *qtab, const int16_t *coef, long n_blocks,
+                   uint8_t *planes, long plane_bytes, const uint64_t *out_ptrs, int32_t *status, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

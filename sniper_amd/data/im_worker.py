@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..jpeg import is_jpeg_path as _is_jpeg
 
 
 def load_bgr(image):
@@ -41,16 +42,36 @@ def _to_device(im):
     return hip.dev(im)
 
 
+DECODERS = ('pil', 'device')
+
+
+def image_decoder(decoder=None, cfg=None):
+    """Who decodes JPEG files: 'pil' (load_bgr on the host, the default) or 'device' (sniper_amd.jpeg: the compressed bytes are uploaded
+    and decoded by kernels, bit for bit the same pixels).  The argument wins, then cfg.IMAGE_DECODER where a config is at hand (read
+    with a default: older configs have no such key), then SNIPER_IMAGE_DECODER."""
+    import os
+    if decoder is None and cfg is not None:
+        decoder = cfg.get('IMAGE_DECODER', None) if hasattr(cfg, 'get') else getattr(cfg, 'IMAGE_DECODER', None)
+    if decoder is None:
+        decoder = os.environ.get('SNIPER_IMAGE_DECODER') or 'pil'
+    if decoder not in DECODERS:
+        raise ValueError("image decoder %r: 'pil' or 'device' required" % (decoder,))
+    return decoder
+
+
 class DeviceImageCache(object):
     """Decoded uint8 images resident on the device, by path (or by object for in-memory arrays).  The reference reads and decodes
     an image once per test scale (lib/data_utils/data_workers.py:49-78 under every scale's iterator); a coarse-to-fine pass visits
     every image at three scales, so `imdb_detection_wrapper` hands ONE cache to the iterators of all its scales: one decode and one
     upload per image and pass (a 5000-image pass of 640 x 480 images is 4.6 GB of a 288 GB card).  Bounded in bytes
-    (SNIPER_IMAGE_CACHE_GB, default 16): the oldest entries go first."""
+    (SNIPER_IMAGE_CACHE_GB, default 16): the oldest entries go first.
+    decoder='device' (image_decoder): JPEG paths are decoded by sniper_amd.jpeg, a batch of them in one call through get_many; arrays,
+    `.npy` files and other formats go the way they always did."""
 
-    def __init__(self, max_bytes=None):
+    def __init__(self, max_bytes=None, decoder=None, cfg=None):
         import os
         import threading
+        self.decoder = image_decoder(decoder, cfg)
         self.max_bytes = int(float(os.environ.get('SNIPER_IMAGE_CACHE_GB', '16')) * (1 << 30)) if max_bytes is None else int(max_bytes)
         self._d, self._bytes, self._lock = {}, 0, threading.Lock()
         self.hits = self.misses = 0
@@ -62,7 +83,14 @@ class DeviceImageCache(object):
             if ent is not None and (isinstance(image, str) or ent[0] is image):
                 self.hits += 1
                 return ent[1]
-        d = _to_device(load_bgr(image))
+        if self.decoder == 'device' and _is_jpeg(image):
+            from ..jpeg import decode_jpeg
+            d = decode_jpeg([image])[0]
+        else:
+            d = _to_device(load_bgr(image))
+        return self._insert(key, image, d)
+
+    def _insert(self, key, image, d):
         n = d.numel() * d.element_size()
         with self._lock:
             ent = self._d.get(key)
@@ -81,6 +109,22 @@ class DeviceImageCache(object):
             self._bytes += n
         return d
 
+    def get_many(self, images, data=None):
+        """the tensors of `images`, in order; with decoder='device' the JPEG paths the cache does not hold are decoded in ONE decode_jpeg
+        call (data: {path: the file's bytes} for those already read).  Everything else goes through get."""
+        if self.decoder == 'device':
+            need, seen = [], set()
+            for im in images:
+                if _is_jpeg(im) and im not in seen and not self.holds(im):
+                    seen.add(im)
+                    need.append(im)
+            if need:
+                from ..jpeg import decode_jpeg
+                got = decode_jpeg([data[im] if data is not None and im in data else im for im in need])
+                for im, d in zip(need, got):
+                    self._insert(im, im, d)
+        return [self.get(im) for im in images]
+
     def holds(self, image):
         key = image if isinstance(image, str) else id(image)
         with self._lock:
@@ -89,6 +133,11 @@ class DeviceImageCache(object):
 
     def __len__(self):
         return len(self._d)
+
+
+def _read_file(path):
+    with open(path, 'rb') as fh:
+        return fh.read()
 
 
 _DECODE_POOLS = {}
@@ -108,6 +157,9 @@ def decode_ahead(worker, images, threads=8):
         need.append(im)
     if len(need) < 2 or threads <= 1:
         return
+    device_jpeg = [im for im in need if _is_jpeg(im)] if cache is not None and cache.decoder == 'device' else []
+    if device_jpeg:
+        need = [im for im in need if not _is_jpeg(im)]
     # ONE pool per (device, thread count) for the process -- not one per caller stream: every PrefetchingIter worker has a stream of
     # its own, and a pool keyed on it leaked eight threads per iterator ever built.  The stream is bound per TASK.
     dev, st = torch.cuda.current_device(), torch.cuda.current_stream()
@@ -123,7 +175,11 @@ def decode_ahead(worker, images, threads=8):
     def task(im):
         with torch.cuda.stream(st):
             return worker._device_image(im)
-    pool.map(task, need, chunksize=1)
+    if device_jpeg:
+        # the threads read the files; one decode_jpeg call uploads and decodes them all
+        cache.get_many(device_jpeg, dict(zip(device_jpeg, pool.map(_read_file, device_jpeg, chunksize=1))))
+    if need:
+        pool.map(task, need, chunksize=1)
 
 
 class im_worker(object):
@@ -132,7 +188,7 @@ class im_worker(object):
         self.crop_size = crop_size
         self.target_size = target_size if target_size else cfg.TRAIN.SCALES[0]
         self.means = np.asarray(cfg.network.PIXEL_MEANS, np.float64)      # (uint8 - float64 in the reference: the subtraction is done in double)
-        self._cache = image_cache if image_cache is not None else DeviceImageCache(256 * 4 << 20)
+        self._cache = image_cache if image_cache is not None else DeviceImageCache(256 * 4 << 20, cfg=cfg)
 
     def _device_image(self, image):
         return self._cache.get(image)

@@ -916,7 +916,7 @@ def _multi_scale_detections(sym_def, config, imdb, roidb, context, arg_params, a
     image_cache = None
     if os.environ.get('SNIPER_IMAGE_CACHE', '1') != '0' and torch.cuda.is_available():
         from .data.im_worker import DeviceImageCache
-        image_cache = DeviceImageCache()
+        image_cache = DeviceImageCache(cfg=config)
     # rows kept in HBM for the device aggregation are CAPACITY buffers ((classes - 1) x RoIs x 40 B per chip: ~1 MB), whatever
     # survives the threshold: a pass over a few hundred images holds a few GB, a 5000-image roidb at the finest scale would ask
     # for more than the card has.  Budget (SNIPER_DEVICE_AGG_GB, default 24): the scale that would exceed it -- and every later
