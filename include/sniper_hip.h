@@ -1063,6 +1063,49 @@ int sn_jpeg_dc(const int32_t *img, const int32_t *h_img, int I, const int32_t *s
 int sn_jpeg_pixels(const int32_t *img, const int32_t *h_img, int I, const uint16_t *qtab, const int16_t *coef, long n_blocks,
                    uint8_t *planes, long plane_bytes, const uint64_t *out_ptrs, int32_t *status, sn_stream_t stream);
 
+/* Baseline JPEG encoding of a batch of pictures: pictures in, the entropy-coded scans of .jpg files out, byte
+ * for byte the scans libjpeg writes at the same quality and sampling (scaled Annex K quantisation tables, slow-integer forward DCT,
+ * Annex K Huffman tables, one interleaved scan, no restart markers).  Integer arithmetic, the same bytes every run; plain vector
+ * stores and 32-bit atomic ORs into zeroed words.  The host writes the headers around the scans (sniper_amd/jpeg_encode.py).
+ * One call takes I pictures of one kind: ncomp 3 (uint8 HWC RGB, as sn_render_dets writes them) or 1 (uint8 grey); picture i has
+ *   hw[i] = (h, w), 1 <= h, w <= 65535, and starts at byte ncomp * pix_off[i] of pix; pix_off (I+1) i64 is the running sum of h * w.
+ *   sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (the luma factors (1,1), (2,1), (2,2); ignored for ncomp 1); quality 1 .. 100.
+ *   Blocks are counted in scan order: MCUs in raster order, inside an MCU the luma blocks row-major, then Cb, then Cr.  blk_off (I+1)
+ *   i64 is the running sum of ceil(w / 8hs) * ceil(h / 8vs) * (hs * vs + ncomp - 1).  hw, pix_off, blk_off are device arrays;
+ *   h_hw, h_pix_off, h_blk_off (HOST) are the same values, which the entry points check against one another.
+ * sn_jpeg_enc_blocks: coef (n_blocks, 64) i16 = the quantised coefficients of every block, zig-zag order inside a block, the DC not
+ *   differenced; a dummy block of an edge MCU (beyond the component's real blocks) has the DC of the last real luma block before it
+ *   in its MCU and no AC.
+ * sn_jpeg_enc_size: bits (n_blocks) i32 = the length of every block's Huffman code.  status (1) i32, zeroed by the caller, collects
+ *   1: a store that had no room, 2: a coefficient no baseline code holds (never, for coefficients sn_jpeg_enc_blocks made).
+ * The caller scans: bit_excl (n_blocks) i64 = the exclusive running sum of bits over the call; pic_first_bit (I) = bit_excl at each
+ *   picture's first block; raw_len (I) i64 = a picture's bits rounded up to bytes; chunk_off (I+1) i64 = the running sum of
+ *   ceil(raw_len / 64): picture i's raw (unstuffed) stream starts at byte 64 * chunk_off[i] of raw.
+ * sn_jpeg_enc_write: every block's code at its bit of raw, MSB first; a picture's last block adds the 1-bits that fill its last byte.
+ *   raw has raw_capacity bytes, ZEROED by the caller, a multiple of 64 and at least the sum over the pictures of (208 * blocks + 1)
+ *   rounded up to 64: a block's code is at most 22 + 63 * 26 bits.  Nothing is written at or past raw + raw_capacity, nor into
+ *   another picture's chunks, whatever the scanned arrays hold.
+ * sn_jpeg_enc_stuff: n_chunks >= chunk_off[I] chunks of 64 bytes.  phase 1: cnt (n_chunks) i32 = the bytes of each chunk after a 00
+ *   is put behind every FF (0 for chunks behind the last).  phase 2: the chunks' stuffed bytes at out + out_pos[chunk] (the caller's
+ *   exclusive running sum of cnt: the pictures' scans lie back to back).  out has `capacity` >= 128 * n_chunks bytes; nothing is
+ *   written at or past out + capacity.
+ * sn_jpeg_enc_limits: h_out8 (HOST) = {threads per workgroup, the largest I, the most blocks per call, raw bytes per block (208),
+ *   bytes per chunk (64), LDS bytes of the blocks kernel, LDS bytes of the size and write kernels, stuffed bytes per raw byte (2)}.
+ * Refused before any launch, by a message that names the function and the condition: NULL pointers; I outside 1 .. 65535; h or w
+ *   outside 1 .. 65535; ncomp, sampling, quality or phase outside their values; offsets or totals that do not follow from the
+ *   sizes; more than 2^22 blocks; capacities below their bounds. */
+int sn_jpeg_enc_limits(int32_t *h_out8);
+int sn_jpeg_enc_blocks(const uint8_t *pix, long total_pixels, const int32_t *hw, const int32_t *h_hw, const int64_t *pix_off,
+                       const int64_t *h_pix_off, const int64_t *blk_off, const int64_t *h_blk_off, int I, long n_blocks, int ncomp,
+                       int sampling, int quality, int16_t *coef, sn_stream_t stream);
+int sn_jpeg_enc_size(const int16_t *coef, const int32_t *hw, const int32_t *h_hw, const int64_t *blk_off, const int64_t *h_blk_off,
+                     int I, long n_blocks, int ncomp, int sampling, int32_t *bits, int32_t *status, sn_stream_t stream);
+int sn_jpeg_enc_write(const int16_t *coef, const int32_t *hw, const int32_t *h_hw, const int64_t *blk_off, const int64_t *h_blk_off,
+                      int I, long n_blocks, int ncomp, int sampling, const int64_t *bit_excl, const int64_t *pic_first_bit,
+                      const int64_t *chunk_off, uint32_t *raw, long raw_capacity, int32_t *status, sn_stream_t stream);
+int sn_jpeg_enc_stuff(const uint32_t *raw, long raw_capacity, const int64_t *chunk_off, const int64_t *raw_len, int I, long n_chunks,
+                      int phase, int32_t *cnt, const int64_t *out_pos, uint8_t *out, long capacity, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -497,7 +497,8 @@ class Tester(object):
         return vis_path or os.path.join(getattr(self.cfg.TEST, 'VISUALIZATION_PATH', os.path.join('debug', 'visualization')), cache_name)
 
     def _vis_encoder(self):
-        """cfg.TEST.VIS_ENCODER: 'pil' (the default) or 'device' -- who encodes the '.png' files of vis=True (visualization._save_all)"""
+        """cfg.TEST.VIS_ENCODER: 'pil' (the default) or 'device' -- who encodes the '.png' and '.jpg' / '.jpeg' files of vis=True
+        (visualization._save_all)"""
         t = self.cfg.TEST
         return t.get('VIS_ENCODER', 'pil') if hasattr(t, 'get') else getattr(t, 'VIS_ENCODER', 'pil')
 

@@ -255,15 +255,21 @@ def _check_encoder(encoder):
 
 
 def _save_all(pics, paths, encoder='pil'):
-    """pics[i] -> paths[i].  encoder='device': a '.png' path (any letter case) is encoded on the device (sniper_amd/png.py), device
-    tensors without their raw bytes coming to the host; every other file, and every file of encoder='pil', is written by PIL."""
+    """pics[i] -> paths[i].  encoder='device': a '.png' path (any letter case) is encoded on the device by sniper_amd/png.py, a '.jpg' or
+    '.jpeg' path by sniper_amd/jpeg_encode.py (byte for byte the file PIL writes: quality 75, 4:2:0), device tensors without their raw
+    bytes coming to the host; every other file, and every file of encoder='pil', is written by PIL."""
     import torch
     _check_encoder(encoder)
-    dev = [k for k, path in enumerate(paths) if encoder == 'device' and os.path.splitext(path)[1].lower() == '.png']
+    ext = [os.path.splitext(path)[1].lower() if encoder == 'device' else '' for path in paths]
+    dev = [k for k, e in enumerate(ext) if e == '.png']
+    jpg = [k for k, e in enumerate(ext) if e in ('.jpg', '.jpeg')]
     if dev:
         from .png import write_png
         write_png([paths[k] for k in dev], [pics[k] for k in dev])
-    for k in sorted(set(range(len(paths))) - set(dev)):
+    if jpg:
+        from .jpeg_encode import write_jpeg
+        write_jpeg([paths[k] for k in jpg], [pics[k] for k in jpg])
+    for k in sorted(set(range(len(paths))) - set(dev) - set(jpg)):
         _save(pics[k].cpu().numpy() if isinstance(pics[k], torch.Tensor) else pics[k], paths[k])
 
 
@@ -272,7 +278,8 @@ def visualize_dets(im, dets, scale, pixel_means, class_names, threshold=0.5, sav
     """The reference's entry point, signature and meaning (lib/data_utils/visualization.py:21-57): transform=True takes the (3, h, w)
     network input and adds pixel_means[[2, 1, 0]] back (transform_im; clamped here); transform=False an (h, w, 3) uint8 RGB image.
     masks[j]: (n, M, M) maps aligned with dets[j].  `dpi` is accepted and unused: a pixel of the image is a pixel of the file.  The
-    file's extension decides its format (PIL); encoder='device' writes a '.png' file with this project's encoder (sniper_amd/png.py).
+    file's extension decides its format (PIL); encoder='device' writes a '.png' file with this project's encoder (sniper_amd/png.py)
+    and a '.jpg' / '.jpeg' file with sniper_amd/jpeg_encode.py, which writes the bytes PIL would.
     -> the (h, w, 3) uint8 picture."""
     import torch
     _check_encoder(encoder)
@@ -303,7 +310,8 @@ def render_results(roidb, all_boxes, class_names, out_dir, all_masks=None, thres
     """A data set's final detections as pictures: image i of roidb (its file `image`, mirrored when `flipped`) with
     all_boxes[j][i] -- and all_masks[j][i], what mask_inference.predict_masks returns -- drawn at scale 1, saved as
     out_dir/{names[i] or i}{vis_ext}.  Images are rendered in batches whose source bytes stay under budget_bytes (one device call
-    each).  encoder='device': '.png' files are encoded on the device, a batch per call, from the rendered pictures where they lie.
+    each).  encoder='device': '.png' and '.jpg' / '.jpeg' files are encoded on the device, a batch per call, from the rendered pictures
+    where they lie (sniper_amd/png.py, sniper_amd/jpeg_encode.py: the JPEG files are byte for byte the files PIL writes).
     -> the paths written, in image order."""
     _check_encoder(encoder)
     if not os.path.isdir(out_dir):
