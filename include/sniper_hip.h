@@ -404,6 +404,8 @@ int sn_ew_f16(const void *a, const void *b, const void *ref, void *y, long rows,
               int mode, sn_stream_t stream);
 /* fp32 element-wise: op 0 a-b, 1 a+b, 2 a*b, 3 a*scalar, 4 fill(scalar). */
 int sn_ew_f32(const float *a, const float *b, float *out, long n, int op, float scalar, sn_stream_t stream);
+/* Max pooling, channels-last fp16: x (N,H,W,C) -> y (N,Ho,Wo,C), Ho = (H + 2 pad - k) / stride + 1; C % 8 == 0 and the window
+ * within the padded input (Ho > 0 && Wo > 0), else SN_ERR_ARG before any launch.  A window with no finite value yields -65504. */
 int sn_maxpool_fwd(const void *x, void *y, int N, int H, int W, int C, int k, int stride, int pad, sn_stream_t stream);
 /* Gradient of sn_maxpool_fwd, channels-last fp16: x (N,H,W,C) the pool's input, dy (N,Ho,Wo,C), dx (N,H,W,C).  The pooled output
  * is not an argument: the decision is re-derived from x.
@@ -422,7 +424,7 @@ int sn_maxpool_bwd(const void *dy, const void *x, const void *accumulate, void *
  * vote over the position-sensitive bins, BASELINE config C4), and its gradient dx = dy / HW (fp16, overwritten). */
 int sn_avgpool_global_fwd(const void *x, float *y, int N, int HW, int C, sn_stream_t stream);
 int sn_avgpool_global_bwd(const float *dy, void *dx, int N, int HW, int C, sn_stream_t stream);
-/* out[b][c][r] = in[b][r][c] with dtype conversion (NHWC <-> NCHW). */
+/* out[b][c][r] = in[b][r][c] with dtype conversion (NHWC <-> NCHW); batch <= 65535 and rows <= 65535 * 32 (grid limits). */
 int sn_transpose_batched(const void *in, void *out, int batch, int rows, int cols, long in_batch_stride, long out_batch_stride,
                          int in_ld, int out_ld, int in_dtype, int out_dtype, sn_stream_t stream);
 int sn_copy2d(const void *in, void *out, long rows, int cols, int in_ld, int out_ld, int in_dtype, int out_dtype,

@@ -734,6 +734,8 @@ SN_EXPORT int sn_ew_f16(const void *a, const void *b, const void *ref, void *y, 
 // ---------------------------------------------------------------------------------------------
 // Max pooling, channels-last fp16 (resnet_mx_101_e2e.py:409: 3x3 stride 2 pad 1).  The backward pass (below the forward one)
 // runs only when something upstream trains: network.FIXED_PARAMS without conv0 / bn0 / stage1.
+// Contract of the forward pass: a window with no finite value (every tap in the padding, or NaN: fmaxf skips it) yields -65504,
+// the lowest finite fp16 value -- not -inf, not NaN.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void maxpool_kernel(const half_t *__restrict__ x, half_t *__restrict__ y, int N, int H,
                                                       int W, int C, int Ho, int Wo, int k, int stride, int pad) {
@@ -769,6 +771,9 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const half_t *__restrict__
 SN_EXPORT int sn_maxpool_fwd(const void *x, void *y, int N, int H, int W, int C, int k, int stride, int pad,
                              sn_stream_t stream) {
   SN_REQUIRE(x && y && C % 8 == 0 && k > 0 && stride > 0, "sn_maxpool_fwd: bad arguments");
+  SN_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k,
+             "sn_maxpool_fwd: the window does not fit the padded input: needs Ho > 0 && Wo > 0 (H = %d, W = %d, k = %d, pad = %d)", H, W, k,
+             pad);
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
   hipLaunchKernelGGL(maxpool_kernel, dim3(ew_blocks((long)N * Ho * Wo * (C / 8))), dim3(256), 0, sn_stream(stream),
                      (const half_t *)x, (half_t *)y, N, H, W, C, Ho, Wo, k, stride, pad);
@@ -1062,6 +1067,7 @@ SN_EXPORT int sn_transpose_batched(const void *in, void *out, int batch, int row
                                    sn_stream_t stream) {
   SN_REQUIRE(in && out && batch > 0 && rows > 0 && cols > 0, "sn_transpose_batched: bad arguments");
   SN_REQUIRE(batch <= 65535, "sn_transpose_batched: batch too large");
+  SN_REQUIRE(sn_div_up(rows, 32) <= 65535, "sn_transpose_batched: too many rows (rows = %d: at most 65535 tiles of 32 rows)", rows);
   dim3 grid(sn_div_up(cols, 32), sn_div_up(rows, 32), batch);
   hipStream_t s = sn_stream(stream);
   if (in_dtype == 0 && out_dtype == 0)

@@ -63,6 +63,19 @@ def test_argument_errors_are_reported_before_any_launch(lib):
         lib.call('sn_dwconv_fwd', ctypes.c_void_p(16), ctypes.c_void_p(16), ctypes.c_void_p(16), 1, 8, 8, 16, 16, 16, 5, 5, 1, 2,
                  1, None)
     assert '3x3' in str(e.value)
+    # the two capped grid dimensions of sn_transpose_batched: z = batch, y = ceil(rows / 32)
+    p = ctypes.c_void_p(16)
+    with pytest.raises(SniperHipError) as e:
+        lib.call('sn_transpose_batched', p, p, 65536, 8, 8, 64, 64, 8, 8, 0, 0, None)
+    assert 'batch too large' in str(e.value)
+    with pytest.raises(SniperHipError) as e:
+        lib.call('sn_transpose_batched', p, p, 1, 65535 * 32 + 1, 8, 0, 0, 8, 65535 * 32 + 1, 0, 0, None)
+    assert 'too many rows' in str(e.value) and str(65535 * 32 + 1) in str(e.value)
+    # a pooling window that does not fit the padded input: no output row (3 + 0 - 5 < 0 would round to Ho = 1 under stride 4)
+    for (H, W, k, s, pad) in ((3, 9, 5, 4, 0), (9, 3, 5, 4, 0), (1, 1, 2, 2, 0), (2, 2, 7, 1, 2)):
+        with pytest.raises(SniperHipError) as e:
+            lib.call('sn_maxpool_fwd', p, p, 1, H, W, 8, k, s, pad, None)
+        assert 'sn_maxpool_fwd' in str(e.value) and 'Ho > 0 && Wo > 0' in str(e.value), (H, W, k, s, pad)
 
 
 def test_roi_pool_and_deform_argument_errors_are_reported_before_any_launch(lib):
