@@ -1108,6 +1108,55 @@ int sn_jpeg_enc_write(const int16_t *coef, const int32_t *hw, const int32_t *h_h
 int sn_jpeg_enc_stuff(const uint32_t *raw, long raw_capacity, const int64_t *chunk_off, const int64_t *raw_len, int I, long n_chunks,
                       int phase, int32_t *cnt, const int64_t *out_pos, uint8_t *out, long capacity, sn_stream_t stream);
 
+/* PNG decoding of a batch of files: zlib streams inflated on the device -- public on its own, the counterpart
+ * of sn_deflate_* -- then the row filters undone and the pixels expanded.  Integer arithmetic, exact bytes, the same every run; no
+ * global atomics, no host read-back inside any call.
+ * sn_inflate: S zlib streams (RFC 1950 / 1951: stored, fixed and dynamic blocks, distances up to 32768) pooled in data (total_in
+ *   bytes).  tab (S, 4) i64 = {in_off, in_len, out_off, out_cap} per stream, given twice as everywhere here: on the device (what the
+ *   kernel reads) and as the HOST array it was uploaded from (h_tab, what the entry point checks).  One wave decodes one stream into
+ *   out + out_off, never at or past out_cap bytes.  meta (S, 2) i32 = {bytes produced, status}; status is 0 or ONE of: 1 bad zlib
+ *   header (CM != 8, window above 32 KiB, FDICT, check bits), 2 block type 3, 4 stored LEN != ~NLEN, 8 bad or over-subscribed code
+ *   lengths (an incomplete set passes only as one code of length 1, as in zlib), 16 invalid symbol (286, 287, distance 30 / 31, a
+ *   code no symbol has), 32 distance beyond the start of the output, 64 input ended early, 128 output over capacity, 256 Adler-32
+ *   mismatch, 512 bytes left after the Adler-32.  A damaged stream ends after a bounded number of steps with its status; what it
+ *   produced before the damage is in out.
+ * sn_inflate_limits: h_out6 (HOST) = {the largest S, the most bytes of a stream and of its output, LDS bytes per wave, the window
+ *   (32768), lanes per stream (64), the bytes after which the window is stored (16384)}.
+ * Images: img (I, 8) i32 = {w, h, bit depth, colour type, row bytes = ceil(w * channels * depth / 8), bpp = max(1, channels * depth
+ *   / 8), palette entries, 0}, raw_off (I) i64 = where the image's h * (row bytes + 1) inflated bytes start in raw; both given on
+ *   the device and on the HOST.  Stream i of the sn_inflate call is image i: meta is the same array.
+ * sn_png_unfilter: the five row filters undone in place (the row above the first and the bytes left of the first pixel are zero,
+ *   Average floors the 9-bit sum, Paeth breaks ties a, b, c).  An image whose status is not 0 is left alone; one whose stream gave
+ *   another length than h * (row bytes + 1) gets status 2048, one with a filter type above 4 status 1024.
+ * sn_png_expand: the images whose status is 0 -> the tensors out_ptrs (I) names.  mode 0: (h, w, 3) uint8 BGR, what PIL's
+ *   convert('RGB') gives reversed (grey of depth 1 / 2 / 4 times 255 / 85 / 17, palette entries from pal (I, 768) with (0, 0, 0)
+ *   beyond `palette entries`, the high byte of 16-bit samples, alpha dropped).  mode 1: (h, w) uint8, the palette index or the grey
+ *   sample scaled to 8 bits; colour types 0 and 3 only.
+ * Refused before any launch, by a message that names the function and the condition: NULL pointers; S or I outside 1 .. 65535;
+ *   streams or outputs that leave their buffers, overlap or exceed the largest stream; sizes, depths, colour types, row bytes or bpp
+ *   that do not fit together; a mode other than 0 / 1. */
+int sn_inflate_limits(int32_t *h_out6);
+int sn_inflate(const uint8_t *data, long total_in, const int64_t *tab, const int64_t *h_tab, long S, uint8_t *out, long out_total,
+               int32_t *meta, sn_stream_t stream);
+int sn_png_unfilter(uint8_t *raw, long raw_total, const int32_t *img, const int32_t *h_img, const int64_t *raw_off,
+                    const int64_t *h_raw_off, int I, int32_t *meta, sn_stream_t stream);
+int sn_png_expand(const uint8_t *raw, long raw_total, const int32_t *img, const int32_t *h_img, const int64_t *raw_off,
+                  const int64_t *h_raw_off, int I, const uint8_t *pal, const uint64_t *out_ptrs, const int32_t *meta, int mode,
+                  sn_stream_t stream);
+
+/* The ground truth of the VOC mask evaluation from index maps (the reference's parse_inst): obj_ptrs / cls_ptrs
+ * (I) u64 name contiguous (h, w) uint8 maps on the device, hw (I, 2) i32 = (h, w) on the device and on the HOST.
+ * sn_vocgt_scan: inst (I, 256, 6) i32 = per instance id {x1, y1, x2, y2 (min / max column / row of the id's pixels), the smallest
+ *   class under them, 1 where they carry more than one class}; x2 = -1 for an id the image does not hold, and for id 0.
+ * sn_vocgt_crop: rec (N, 6) i32 = {image, id, x1, y1, bound width, bound height}, pool_off (N + 1) i64 = the running sum of width *
+ *   height (both on the device and on the HOST) -> pool[pool_off[n] + y * width + x] = 1 where the object map holds the id.
+ * Refused before any launch: NULL pointers; I outside 1 .. 65535, N outside 1 .. 65535; empty maps; a bound that leaves its map;
+ *   offsets that are not the running sum. */
+int sn_vocgt_scan(const uint64_t *obj_ptrs, const uint64_t *cls_ptrs, const int32_t *hw, const int32_t *h_hw, int I, int32_t *inst,
+                     sn_stream_t stream);
+int sn_vocgt_crop(const uint64_t *obj_ptrs, const int32_t *hw, const int32_t *h_hw, int I, const int32_t *rec, const int32_t *h_rec,
+                     const int64_t *pool_off, const int64_t *h_pool_off, long N, uint8_t *pool, long pool_total, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ import torch
 
 from .. import hip
 from ..jpeg import is_jpeg_path as _is_jpeg
+from ..png_decode import is_png_path as _is_png
 
 
 def load_bgr(image):
@@ -46,9 +47,9 @@ DECODERS = ('pil', 'device')
 
 
 def image_decoder(decoder=None, cfg=None):
-    """Who decodes JPEG files: 'pil' (load_bgr on the host, the default) or 'device' (sniper_amd.jpeg: the compressed bytes are uploaded
-    and decoded by kernels, bit for bit the same pixels).  The argument wins, then cfg.IMAGE_DECODER where a config is at hand (read
-    with a default: older configs have no such key), then SNIPER_IMAGE_DECODER."""
+    """Who decodes JPEG and PNG files: 'pil' (load_bgr on the host, the default) or 'device' (sniper_amd.jpeg, sniper_amd.png_decode:
+    the compressed bytes are uploaded and decoded by kernels, bit for bit the same pixels).  The argument wins, then
+    cfg.IMAGE_DECODER where a config is at hand (read with a default: older configs have no such key), then SNIPER_IMAGE_DECODER."""
     import os
     if decoder is None and cfg is not None:
         decoder = cfg.get('IMAGE_DECODER', None) if hasattr(cfg, 'get') else getattr(cfg, 'IMAGE_DECODER', None)
@@ -65,8 +66,8 @@ class DeviceImageCache(object):
     every image at three scales, so `imdb_detection_wrapper` hands ONE cache to the iterators of all its scales: one decode and one
     upload per image and pass (a 5000-image pass of 640 x 480 images is 4.6 GB of a 288 GB card).  Bounded in bytes
     (SNIPER_IMAGE_CACHE_GB, default 16): the oldest entries go first.
-    decoder='device' (image_decoder): JPEG paths are decoded by sniper_amd.jpeg, a batch of them in one call through get_many; arrays,
-    `.npy` files and other formats go the way they always did."""
+    decoder='device' (image_decoder): JPEG paths are decoded by sniper_amd.jpeg and `.png` paths by sniper_amd.png_decode, a batch of
+    them in one call through get_many; arrays, `.npy` files and other formats go the way they always did."""
 
     def __init__(self, max_bytes=None, decoder=None, cfg=None):
         import os
@@ -86,6 +87,9 @@ class DeviceImageCache(object):
         if self.decoder == 'device' and _is_jpeg(image):
             from ..jpeg import decode_jpeg
             d = decode_jpeg([image])[0]
+        elif self.decoder == 'device' and _is_png(image):
+            from ..png_decode import decode_png
+            d = decode_png([image])[0]
         else:
             d = _to_device(load_bgr(image))
         return self._insert(key, image, d)
@@ -111,18 +115,20 @@ class DeviceImageCache(object):
 
     def get_many(self, images, data=None):
         """the tensors of `images`, in order; with decoder='device' the JPEG paths the cache does not hold are decoded in ONE decode_jpeg
-        call (data: {path: the file's bytes} for those already read).  Everything else goes through get."""
+        call and the `.png` paths in ONE decode_png call (data: {path: the file's bytes} for those already read).  Everything else
+        goes through get."""
         if self.decoder == 'device':
-            need, seen = [], set()
-            for im in images:
-                if _is_jpeg(im) and im not in seen and not self.holds(im):
-                    seen.add(im)
-                    need.append(im)
-            if need:
-                from ..jpeg import decode_jpeg
-                got = decode_jpeg([data[im] if data is not None and im in data else im for im in need])
-                for im, d in zip(need, got):
-                    self._insert(im, im, d)
+            from .. import jpeg, png_decode
+            for is_kind, decode in ((_is_jpeg, jpeg.decode_jpeg), (_is_png, png_decode.decode_png)):
+                need, seen = [], set()
+                for im in images:
+                    if is_kind(im) and im not in seen and not self.holds(im):
+                        seen.add(im)
+                        need.append(im)
+                if need:
+                    got = decode([data[im] if data is not None and im in data else im for im in need])
+                    for im, d in zip(need, got):
+                        self._insert(im, im, d)
         return [self.get(im) for im in images]
 
     def holds(self, image):
