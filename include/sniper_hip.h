@@ -937,6 +937,23 @@ int sn_grad_guard_scaled(const float *d_grad, long n, const float *d_hyper, floa
                          double growth_factor, double backoff_factor, double min_scale, double max_scale, void *d_ws, double *d_state,
                          double *d_ls, sn_stream_t stream);
 int sn_aux_shadow(const void *desc, int n_desc, float *d_shadow, int mode, const double *d_state, sn_stream_t stream);
+/* Gradient accumulation: the gradient arena of one micro-batch copied into, or added onto, a second arena, so that the guard and the
+ * update above run once per k micro-batches on the sum (what k data-parallel ranks and a summing all-reduce compute).
+ * sn_grad_accumulate: one launch over n fp32.  d_grad [0, n) is read; d_acc [0, n) is written, and read first unless `first`; nothing
+ *   else is touched.  first != 0: d_acc[i] = d_grad[i] as a copy of the 32 bits (NaN payloads and -0 included).  first == 0:
+ *   d_acc[i] = d_acc[i] + d_grad[i], one IEEE binary32 addition rounded to nearest even; subnormal inputs and results are kept, not
+ *   flushed; inf and NaN propagate (inf + -inf = NaN), which is how the guard sees a poisoned micro-batch at the end of the window.
+ *   Both pointers need 4-byte alignment only and may sit at DIFFERENT offsets from a 16-byte boundary.  The split follows d_acc: its
+ *   0-3 elements in front of a 16-byte boundary one at a time, then 16-byte stores (and loads of d_acc), then a tail of 0-3.  d_grad
+ *   is read 16 bytes wide where it has d_acc's offset modulo 16 bytes, otherwise with four 4-byte loads per 16-byte store.
+ *   Grid-stride loop; max_blocks: 0 = the library's grid, a fixed function of n; > 0 caps the grid (<= 65535).  No atomics, no LDS, no
+ *   workspace: every element belongs to one thread, so the bits are the same for every grid, alignment and run -- those of the
+ *   statement above (the copy exactly; the sum exactly where it is not NaN, some NaN where it is).
+ *   Refused before any launch: a null pointer with n > 0, n < 0, a pointer that is not 4-byte aligned, max_blocks outside
+ *   0 .. 65535, and ranges [d_acc, d_acc + n) and [d_grad, d_grad + n) that overlap.  n == 0: no launch, success.
+ * sn_grad_accumulate_limits: h_out3 (HOST) = {threads per block, floats per thread per trip, the default grid cap}. */
+int sn_grad_accumulate_limits(int32_t *h_out3);
+int sn_grad_accumulate(float *d_acc, const float *d_grad, long n, int first, int max_blocks, sn_stream_t stream);
 /* fp32 [O][T][I] -> fp16 [I][T][O_pad] (weights for sn_conv_dgrad; O_pad = O rounded up to 8, zero filled). */
 int sn_weight_transpose(const float *w_oti, void *wt_ito_f16, int O, int T, int I, int O_pad, sn_stream_t stream);
 /* The same transposition for MANY weights in one launch (the optimizer step re-emits every data-gradient copy).  desc is a

@@ -261,6 +261,7 @@ class Executor(object):
         self._hyper_host = None       # update: the values self.hyper holds
         self.guard = None             # set_grad_guard: thresholds, device state and workspace of the gradient guard
         self.loss_scale = None        # set_loss_scale: policy, device scaler state, table and shadow of the forward's side effects
+        self.accum = None             # set_accumulate(k > 1): k, the accumulation arena, the micro-steps pending in it
         self._lower()
         self._mark_half_region()
         self.split_k = self._choose_split() if (split_backward and for_training) else 0
@@ -855,12 +856,20 @@ class Executor(object):
             v.grad = None
             v.grad_group = None
         ls = self.loss_scale
-        if ls is not None and ls['n_aux'] and self.is_train:
+        if ls is not None and ls['n_aux'] and self.is_train and self.accum is None:
             # the moving statistics as they are before this forward rewrites them: a step the guard skips puts them back (_update_body)
             hip.call('sn_aux_shadow', ls['table'], ls['n_aux'], ls['shadow'], 0, None, hip.stream())
         for s in self.steps:
             s.forward()
         self.outputs = [self.as_f32(self.vals[(id(n), i)]) for n, i in self.sym._heads]
+
+    def _save_aux_for_window(self):
+        """Accumulating (set_accumulate(k > 1)) with restore_aux: the moving statistics are saved before the FIRST micro-step of a
+        window only -- one eager launch in front of the replayed graph instead of the save inside _forward_body --, so that a skipped
+        window puts back what they were before the window, not before its last micro-batch."""
+        ls = self.loss_scale
+        if self.accum is not None and self.accum['pending'] == 0 and ls is not None and ls['n_aux']:
+            hip.call('sn_aux_shadow', ls['table'], ls['n_aux'], ls['shadow'], 0, None, hip.stream())
 
     def forward(self, inputs, is_train=None):
         is_train = self.for_training if is_train is None else is_train
@@ -907,6 +916,8 @@ class Executor(object):
                 finally:
                     if gc_was:
                         gc.enable()
+        if is_train:
+            self._save_aux_for_window()
         self._forward_body()
         return self.outputs
 
@@ -969,6 +980,7 @@ class Executor(object):
         starts the all-reduce of the finished gradients there, on its own stream, while the second segment runs."""
         self.is_train = True
         self.load_inputs(inputs)
+        self._save_aux_for_window()
         if not self.split_k:
             if self._graph_fb is not None:
                 self._graph_fb.replay()
@@ -1100,22 +1112,60 @@ class Executor(object):
                            'table': torch.from_numpy(rec.view(np.uint8).copy()).to(self.device) if len(aux) else None,
                            'shadow': self.zeros((max(off, 8),), F32)}
 
+    @staticmethod
+    def check_accumulate(k):
+        """ValueError unless k is what set_accumulate takes: an int >= 1 (no bool, no float)"""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+            raise ValueError('accumulate must be an int >= 1, got %r' % (k,))
+        return int(k)
+
+    def set_accumulate(self, k):
+        """Gradient accumulation (DESIGN.md "Gradient accumulation"): one optimizer update per k micro-batches, on the SUM of their
+        gradients -- what k data-parallel ranks and a summing all-reduce compute: every micro-batch has its own BatchNorm statistics
+        and loss normalisation, nothing is averaged (rescale_grad = 1 / k does that).  k > 1 allocates a second arena of the gradient
+        arena's size; accumulate() after every forward_backward copies (first micro-step of a window) or adds the gradient arena into
+        it with one sn_grad_accumulate beside the replayed forward/backward graph, and update() -- guard, loss-scale finalize and SGD
+        alike -- reads that arena and applies whatever is pending.  The gradient writers and the captured forward/backward graph are
+        untouched.  With restore_aux the moving statistics are saved before the first micro-step of a window (_save_aux_for_window).
+        k = 1 drops the arena: the step is the one it was before.  Either way a window starts anew and the captured optimizer graph is
+        dropped (it holds the arena's address), the forward/backward graph only where the save of the moving statistics moves."""
+        k = Executor.check_accumulate(k)
+        moves_save = (self.accum is None) != (k == 1) and self.loss_scale is not None and self.loss_scale['n_aux']
+        self._graph_up = None
+        if moves_save:
+            self._graph_fb = None
+        if k == 1:
+            self.accum = None
+            return
+        self.accum = {'k': k, 'arena': self.zeros((self.arena_grad.numel(),), F32), 'pending': 0}
+
+    def accumulate(self):
+        """After a forward_backward: this micro-batch's gradients into the accumulation arena -> the micro-steps now pending"""
+        a = self.accum
+        if a is None:
+            raise RuntimeError('accumulate() without set_accumulate(k > 1)')
+        hip.call('sn_grad_accumulate', a['arena'], self.arena_grad, self.arena_grad.numel(), 1 if a['pending'] == 0 else 0, 0,
+                 hip.stream())
+        a['pending'] += 1
+        return a['pending']
+
     def _update_body(self, lr=None, wd=None, momentum=None, rescale_grad=None):
         g, ls = self.guard, self.loss_scale
+        grad = self.accum['arena'] if self.accum is not None else self.arena_grad
         if ls is not None:
-            hip.call('sn_grad_guard_scaled', self.arena_grad, self.arena_grad.numel(), self.hyper, g['clip_global_norm'], 0,
+            hip.call('sn_grad_guard_scaled', grad, grad.numel(), self.hyper, g['clip_global_norm'], 0,
                      ls['growth_interval'], ls['growth_factor'], ls['backoff_factor'], ls['min_scale'], ls['max_scale'], g['ws'],
                      g['state'], ls['state'], hip.stream())
         elif g is not None:
-            hip.call('sn_grad_guard', self.arena_grad, self.arena_grad.numel(), self.hyper, g['clip_global_norm'], g['skip_nonfinite'],
+            hip.call('sn_grad_guard', grad, grad.numel(), self.hyper, g['clip_global_norm'], g['skip_nonfinite'],
                      0, g['ws'], g['state'], hip.stream())
         for (lr_mult, wd_mult, _half), a, b in self.groups:
             if g is not None:
-                hip.call('sn_sgd_mom_update_guarded_dev', self.arena_master[a:], self.arena_grad[a:], self.arena_mom[a:],
+                hip.call('sn_sgd_mom_update_guarded_dev', self.arena_master[a:], grad[a:], self.arena_mom[a:],
                          self.arena_w16[a:], b - a, self.hyper, float(lr_mult), float(wd_mult), g['clip_gradient'], g['state'],
                          hip.stream())
                 continue
-            hip.call('sn_sgd_mom_update_dev', self.arena_master[a:], self.arena_grad[a:], self.arena_mom[a:], self.arena_w16[a:],
+            hip.call('sn_sgd_mom_update_dev', self.arena_master[a:], grad[a:], self.arena_mom[a:], self.arena_w16[a:],
                      b - a, self.hyper, float(lr_mult), float(wd_mult), hip.stream())
         if ls is not None and ls['n_aux']:
             hip.call('sn_aux_shadow', ls['table'], ls['n_aux'], ls['shadow'], 1, g['state'], hip.stream())
@@ -1126,6 +1176,12 @@ class Executor(object):
         # Hyper-parameters live on the device (the captured optimizer graph reads them).  They are written by fill kernels
         # with the value as a launch argument, and only when they change: a host-to-device copy from pageable memory makes
         # the host wait for everything already queued on the stream, i.e. for the whole previous step.
+        if self.accum is not None:
+            # accumulating: the pass reads the accumulation arena and applies whatever is pending there (1 .. k micro-steps)
+            if self.accum['pending'] == 0:
+                raise RuntimeError('update() with no accumulated micro-step pending (set_accumulate(%d): accumulate() first)'
+                                   % self.accum['k'])
+            self.accum['pending'] = 0
         vals = (float(lr), float(wd), float(momentum), float(rescale_grad))
         last = self._hyper_host
         for i, v in enumerate(vals):
@@ -1145,5 +1201,5 @@ class Executor(object):
         self._eager_up += 1
 
     def grad_arena(self):
-        """Flat fp32 gradient buffer (what the data-parallel all-reduce sums)."""
-        return self.arena_grad
+        """Flat fp32 gradient buffer (what the data-parallel all-reduce sums): while accumulating, the accumulation arena."""
+        return self.accum['arena'] if self.accum is not None else self.arena_grad

@@ -144,6 +144,7 @@ class Module(object):
                 else:
                     ex.set_params(self._arg_params, self._aux_params)
             self._guard_exe(ex)
+            self._accum_exe(ex)
             self._exes[key] = ex
             if not self.for_training:
                 self._evict_stale(keep=ex)
@@ -245,6 +246,9 @@ class Module(object):
     def save_checkpoint(self, prefix, epoch, save_optimizer_states=False):
         if self.rank != 0:
             return
+        if save_optimizer_states and getattr(self, '_accum_pending', 0) > 0:
+            self.logger.warning('gradient accumulation: %d of %d micro-batches are pending; their gradients are not in the .states file, '
+                                'a resumed run starts a new window', self._accum_pending, self.opt['accumulate'])
         arg, aux = self.get_params()
         save_checkpoint(prefix, epoch, self.symbol, arg, aux)
         if save_optimizer_states:
@@ -265,13 +269,50 @@ class Module(object):
                     'momentum': float(op.get('momentum', 0.0)), 'rescale_grad': float(op.get('rescale_grad', 1.0)),
                     'lr_scheduler': op.get('lr_scheduler')}
         self.opt.update(guard)
+        self.opt['accumulate'] = self._accumulate_option(op)
         if self.opt['lr_scheduler'] is not None:
             self.opt['lr_scheduler'].base_lr = self.opt['lr']
         self.optimizer_initialized = True
         self._guard_host = None
         self._loss_scale_resume = None
+        self._accum_pending = self._accum_updates = 0
         for ex in getattr(self, '_exes', {}).values():
             self._guard_exe(ex)
+            self._accum_exe(ex)
+
+    # ---- gradient accumulation (Executor.set_accumulate): optimizer parameter accumulate = k, one update per k micro-batches on the
+    # SUM of their gradients (k micro-batches = k ranks).  Without the key, SNIPER_ACCUMULATE is read here, once: the way the
+    # reference's unchanged main_train.py turns it on.  The key wins over the variable.
+    @staticmethod
+    def _accumulate_option(op):
+        from ..engine.executor import Executor
+        if op.get('accumulate') is not None:              # (None is "absent", as for the guard's options)
+            return Executor.check_accumulate(op['accumulate'])
+        env = os.environ.get('SNIPER_ACCUMULATE')
+        if env is None or not env.strip():
+            return 1
+        try:
+            k = int(env.strip())
+        except ValueError:
+            raise ValueError('SNIPER_ACCUMULATE must be an int >= 1, got %r' % (env,))
+        return Executor.check_accumulate(k)
+
+    def _accum_exe(self, ex):
+        """the optimizer's accumulate option -> a training executor (where _guard_exe is called); k = 1 on an executor that does not
+        accumulate touches nothing"""
+        opt = getattr(self, 'opt', None)
+        if opt is None or not ex.for_training:
+            return
+        k = opt.get('accumulate', 1)
+        if k > 1 or ex.accum is not None:
+            ex.set_accumulate(k)
+
+    def accumulate_state(self):
+        """{'k': micro-batches per update, 'pending': micro-batches accumulated since the last update, 'updates': optimizer updates
+        so far}.  Metrics, Speedometer and the guard's lagged snapshots stay per micro-batch / per update as they are."""
+        opt = getattr(self, 'opt', None) or {}
+        return {'k': int(opt.get('accumulate', 1)), 'pending': int(getattr(self, '_accum_pending', 0)),
+                'updates': int(getattr(self, '_accum_updates', 0))}
 
     # ---- gradient guard (Executor.set_grad_guard): clip_gradient is mx 'sgd's parameter; clip_global_norm, skip_nonfinite and
     # max_consecutive_skips are this engine's
@@ -561,7 +602,9 @@ class Module(object):
         """The training step's compute: one hipGraph replay once the executor has captured it (two with a split
         backward: the first segment's gradient all-reduce is started between them)."""
         self._comm_event = None
-        self.exe.forward_backward(self._feed(data_batch), between=self._allreduce_first_segment if self.exe.split_k else None)
+        # accumulating: no overlap -- the first segment's all-reduce would run per micro-step and be summed k times for nothing
+        overlap = self.exe.split_k and (getattr(self, 'opt', None) or {}).get('accumulate', 1) == 1
+        self.exe.forward_backward(self._feed(data_batch), between=self._allreduce_first_segment if overlap else None)
 
     def _half_buf(self):
         exe = self.exe
@@ -593,6 +636,14 @@ class Module(object):
 
     def update(self):
         from ..parallel import allreduce_ranges
+        k = self.opt.get('accumulate', 1)
+        if k > 1:
+            # one micro-step of a window of k: its gradients go into the accumulation arena; until the k-th nothing else happens (no
+            # all-reduce, no scheduler call, no optimizer launch, no snapshot).  The k-th all-reduces the SUM once (grad_arena() is
+            # the accumulation arena) and updates.  The window ignores epochs: a partial one carries over.
+            self._accum_pending = self.exe.accumulate()
+            if self._accum_pending < k:
+                return
         d = _dist()
         if d is not None and d.get_world_size() > 1:          # sum over ranks == kvstore 'device' push/pull
             exe = self.exe
@@ -611,6 +662,8 @@ class Module(object):
         lr = sched(self.exe.num_update + 1) if sched is not None else self.opt['lr']
         # (the guard, when set, is the first thing the optimizer pass runs: behind the all-reduce, so every rank decides on the same sum)
         self.exe.update(lr, self.opt['wd'], self.opt['momentum'], self.opt['rescale_grad'])
+        self._accum_pending = 0
+        self._accum_updates = getattr(self, '_accum_updates', 0) + 1
         if self.exe.guard is not None:
             self._guard_snapshot()
 

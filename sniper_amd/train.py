@@ -42,6 +42,9 @@ def optimizer_params(cfg, lr_scheduler=None):
     # arena holds gradients multiplied by the static loss scale: the two thresholds are in those units.
     guard = {'clip_gradient': getattr(tr, 'CLIP_GRADIENT', None), 'clip_global_norm': getattr(tr, 'CLIP_GLOBAL_NORM', None),
              'skip_nonfinite': bool(getattr(tr, 'SKIP_NONFINITE', False))}
+    # gradient accumulation: TRAIN.ACCUMULATE = k, one update per k batches on the sum of their gradients -- a key the reference's
+    # configs do not have; absent (None) leaves the choice to SNIPER_ACCUMULATE, else 1 (Module.init_optimizer)
+    guard['accumulate'] = getattr(tr, 'ACCUMULATE', None)
     dyn = dynamic_loss_scale(cfg)
     if dyn is not None:
         # the scale lives on the device and the update divides it out again: lr and wd are the true ones, nothing is folded, and
@@ -70,13 +73,20 @@ class Trainer(object):
     clipped -- thresholds in the arena's units, i.e. times TRAIN.scale with fp16.
     `dynamic_loss_scale` (True, or a dict of Executor.set_loss_scale's arguments; TRAIN.DYNAMIC_SCALE) replaces the static loss scale
     by one the device keeps: halved when a step overflows -- that step is skipped and leaves the BatchNorm moving statistics as they
-    were --, doubled after growth_interval clean steps; lr, wd and the guard's thresholds are then in true units."""
+    were --, doubled after growth_interval clean steps; lr, wd and the guard's thresholds are then in true units.
+    `accumulate=k` (TRAIN.ACCUMULATE; None keeps the config's key, absent means 1) updates once per k steps, on the SUM of the k
+    batches' gradients: k x BATCH_IMAGES chips per update, summed like k data-parallel ranks -- every batch keeps its own BatchNorm
+    statistics and loss normalisation, nothing is averaged, and the schedule counts the update once.  So the reference's lr,
+    warmup_step and lr_step hold when k x BATCH_IMAGES equals the reference's global batch; whoever wants the mean sets
+    rescale_grad = 1 / k.  The guard and the dynamic loss scale judge the window's sum, once per window."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
                  fix_bn=False, fixed_params=None, ohem=None, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False,
-                 dynamic_loss_scale=None):
+                 dynamic_loss_scale=None, accumulate=None):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
+        if accumulate is not None:
+            cfg.TRAIN.ACCUMULATE = accumulate
         if dynamic_loss_scale is not None and dynamic_loss_scale is not False:
             cfg.TRAIN.DYNAMIC_SCALE = dynamic_loss_scale       # (before the symbol is built: its grad_scale attributes become 1 x)
         if clip_gradient is not None:
