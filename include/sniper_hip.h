@@ -954,6 +954,43 @@ int sn_aux_shadow(const void *desc, int n_desc, float *d_shadow, int mode, const
  * sn_grad_accumulate_limits: h_out3 (HOST) = {threads per block, floats per thread per trip, the default grid cap}. */
 int sn_grad_accumulate_limits(int32_t *h_out3);
 int sn_grad_accumulate(float *d_acc, const float *d_grad, long n, int first, int max_blocks, sn_stream_t stream);
+/* Per-tensor statistics of a flat arena: where in the gradient arena a non-finite value sits, and the norms
+ * mx.mon.Monitor prints -- one read of the arena, deterministic, capturable.
+ * sn_tensor_stats_limits: h_out6 (HOST) = {fp32 elements per block trip, elements per chunk, the largest T, doubles per record (8),
+ *   fp16 elements per block trip, the default grid cap of the pass}.
+ * sn_tensor_stats_plan (HOST only, no device call): h_segs = T records {int64 off; int64 n} (16 bytes each, offsets in ELEMENTS):
+ *   disjoint, in any order, n = 0 allowed.  A work item is a chunk of at most `elements per chunk` elements of ONE tensor; a tensor of
+ *   n elements has ceil(n / chunk) items (none for n = 0), in ascending order, tensor after tensor in table order.  h_plan == NULL:
+ *   the table is checked and *h_n_items = the number of items; else the plan is also written to h_plan (8-byte aligned,
+ *   plan_bytes >= sn_tensor_stats_plan_bytes(T, n_items)): n_items 32-byte items {int64 off; int64 off_in_tensor; int32 len;
+ *   int32 tensor; 8 bytes of zeros}, then T 16-byte tensors {int64 n; int32 first_item; int32 items}.  The caller uploads it once per
+ *   table.  Refused with a message: T outside 0 .. the limit, a negative off or n, off + n past 2^63 - 1, overlapping segments, more
+ *   than 2^31 - 1 items, a plan buffer that is too small.
+ * sn_tensor_stats_workspace_bytes(T, n_items): the bytes of d_ws (one 64-byte partial record per item), 0 for arguments out of range.
+ * sn_tensor_stats: two launches on `stream`, no host copy, no wait.  d_x: the arena (dtype 0 = fp16, 1 = fp32; aligned to its
+ *   element size: every item is peeled to a 16-byte boundary, then read with 16-byte loads; elements between segments are never part
+ *   of a record).  d_plan: the uploaded plan.  max_blocks: 0 = the library's grid cap, > 0 caps the grid of the pass (<= 65535).
+ *   d_out, (1 + T, 8) float64, 8-byte aligned: a header row, then one record per tensor in table order.
+ *     header [0] 1.0: this launch wrote the records   [1] d_guard_state[4] (the guard's step counter), 0 without a state   [2] T
+ *            [3] tensors with a non-finite element    [4] the table index of the first such tensor, -1 if none          [5..7] 0
+ *     record, an element x being finite iff fabsf(x) <= FLT_MAX (the guard's rule):
+ *            [0] sumsq: sum of (double)x * x over the finite elements       [1] sum of (double)x over the finite elements
+ *            [2] non-finite elements (exact)    [3] index inside the tensor of the first non-finite element, -1 if none (exact)
+ *            [4] max |x| over the finite elements, 0 if none (exact)        [5] elements equal to zero, -0.0 included (exact)
+ *            [6] n                              [7] 0
+ *   The two float sums are fp64 per thread, wave, block and item (one block reduces one item in a fixed order), and a tensor's item
+ *   partials are added in item order: no floating-point atomics, and for a given table, dtype and d_x modulo 16 bytes the same bits
+ *   every run and for EVERY max_blocks.
+ *   only_if_skipped != 0 (needs d_guard_state, the eight doubles of sn_grad_guard): every block of both launches reads
+ *   d_guard_state[2] (skip) before its first load and returns when it is 0: d_out and d_ws are then left untouched, bit for bit.
+ *   Refused before any launch: null d_x / d_plan / d_ws / d_out, a dtype other than 0 / 1, T or max_blocks out of range, n_items < 0,
+ *   only_if_skipped without a state, misaligned pointers. */
+int sn_tensor_stats_limits(int32_t *h_out6);
+int sn_tensor_stats_plan(const int64_t *h_segs, int T, void *h_plan, size_t plan_bytes, int32_t *h_n_items);
+size_t sn_tensor_stats_plan_bytes(int T, int n_items);
+size_t sn_tensor_stats_workspace_bytes(int T, int n_items);
+int sn_tensor_stats(const void *d_x, int dtype, const void *d_plan, int n_items, int T, int max_blocks, const double *d_guard_state,
+                    int only_if_skipped, void *d_ws, double *d_out, sn_stream_t stream);
 /* fp32 [O][T][I] -> fp16 [I][T][O_pad] (weights for sn_conv_dgrad; O_pad = O rounded up to 8, zero filled). */
 int sn_weight_transpose(const float *w_oti, void *wt_ito_f16, int O, int T, int I, int O_pad, sn_stream_t stream);
 /* The same transposition for MANY weights in one launch (the optimizer step re-emits every data-gradient copy).  desc is a

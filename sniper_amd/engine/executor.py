@@ -14,7 +14,9 @@ runtime (component 10): executor, operator kernels, optimiz
 * torch provides device memory, streams and (elsewhere) torch.distributed; every byte of compute
   goes through the C ABI (sniper_amd.hip.call).  No CPU fallback.
 """
+import ctypes
 import os
+import re
 import warnings
 
 import numpy as np
@@ -262,6 +264,8 @@ class Executor(object):
         self.guard = None             # set_grad_guard: thresholds, device state and workspace of the gradient guard
         self.loss_scale = None        # set_loss_scale: policy, device scaler state, table and shadow of the forward's side effects
         self.accum = None             # set_accumulate(k > 1): k, the accumulation arena, the micro-steps pending in it
+        self.skip_report = None       # set_skip_report(True): the table and the report buffer of the skipped step's per-tensor statistics
+        self._stat_tables = {}        # stat_table: (pattern, suffix) -> names, segments, uploaded plan, workspace, output buffers
         self._lower()
         self._mark_half_region()
         self.split_k = self._choose_split() if (split_backward and for_training) else 0
@@ -1036,6 +1040,8 @@ class Executor(object):
         self._graph_up = None
         if self.loss_scale is not None:
             skip_nonfinite = True                  # (dynamic loss scaling implies it: set_loss_scale)
+        if not skip_nonfinite:
+            self.skip_report = None                # (the report rides behind a guard that skips)
         if clip_gradient is None and clip_global_norm is None and not skip_nonfinite:
             self.guard = None
             return
@@ -1149,6 +1155,120 @@ class Executor(object):
         a['pending'] += 1
         return a['pending']
 
+    # ---- per-tensor statistics (DESIGN.md "Per-tensor statistics"): sn_tensor_stats over one of the four arenas
+    STAT_ARENAS = ('grad', 'weight', 'mom', 'w16')
+
+    def _stat_arena(self, which):
+        if which == 'grad':
+            return self.grad_arena()              # (while accumulating: the accumulation arena)
+        if which not in self.STAT_ARENAS:
+            raise ValueError('tensor statistics: arena %r, known: %s' % (which, ', '.join(self.STAT_ARENAS)))
+        return {'weight': self.arena_master, 'mom': self.arena_mom, 'w16': self.arena_w16}[which]
+
+    def _plan_stats(self, names, segs):
+        """a segment table [(offset, numel), ...] -> the plan of sn_tensor_stats, uploaded once, with the workspace its launches use"""
+        lib = hip.lib()
+        T = len(segs)
+        seg = np.ascontiguousarray(np.asarray(segs, np.int64).reshape(T, 2))
+        n_items = ctypes.c_int32(0)
+        lib.call('sn_tensor_stats_plan', seg.ctypes.data, T, None, 0, ctypes.byref(n_items))      # (host only: refuses a bad table)
+        n_items = int(n_items.value)
+        nbytes = int(lib.raw('sn_tensor_stats_plan_bytes')(T, n_items))
+        plan = np.zeros(max(nbytes, 8) // 8 + 1, np.int64)
+        lib.call('sn_tensor_stats_plan', seg.ctypes.data, T, plan.ctypes.data, nbytes, ctypes.byref(ctypes.c_int32(0)))
+        return {'names': list(names), 'segs': seg, 'T': T, 'n_items': n_items,
+                'plan': torch.from_numpy(plan).to(self.device),
+                'ws': self.empty((int(lib.raw('sn_tensor_stats_workspace_bytes')(T, n_items)),), torch.uint8), 'out': {}}
+
+    def stat_table(self, pattern=None, suffix=''):
+        """The trainable parameters whose name + suffix the regular expression matches at its start (re.match, as mx.mon.Monitor does;
+        None: all of them), in arena order: {'names', 'segs' (T, 2) int64 offsets and lengths in elements -- Param.offset, Param.numel,
+        the padding between tensors is in no segment --, 'T', 'n_items', 'plan', 'ws'}.  The four arenas share one layout, so a table
+        serves all of them.  Built at the first use and kept."""
+        key = (pattern, suffix)
+        tab = self._stat_tables.get(key)
+        if tab is None:
+            prog = re.compile(pattern) if pattern is not None else None
+            ps = sorted((p for p in self.params.values() if p.trainable), key=lambda p: p.offset)
+            ps = [p for p in ps if prog is None or prog.match(p.name + suffix)]
+            tab = self._stat_tables[key] = self._plan_stats([p.name for p in ps], [(p.offset, p.numel) for p in ps])
+        return tab
+
+    @property
+    def stat_tables(self):
+        """arena -> the table of all trainable parameters (one object: the arenas share their layout)"""
+        tab = self.stat_table()
+        return {which: tab for which in self.STAT_ARENAS}
+
+    def _run_stats(self, x, tab, slot, guard_state=None, only_if_skipped=0):
+        out = tab['out'].get(slot)
+        if out is None:
+            out = tab['out'][slot] = self.zeros((1 + tab['T'], 8), torch.float64)
+        hip.call('sn_tensor_stats', x, 1 if x.dtype == F32 else 0, tab['plan'], tab['n_items'], tab['T'], 0, guard_state,
+                 only_if_skipped, tab['ws'], out, hip.stream())
+        return out
+
+    def tensor_stats(self, which, pattern=None, suffix=''):
+        """One sn_tensor_stats launch pair on the current stream over arena `which` ('grad', 'weight' = the fp32 masters, 'mom', 'w16')
+        -> (the device tensor (1 + T, 8) float64 of include/sniper_hip.h, the parameter names of its records).  Does not synchronise;
+        the tensor belongs to the table and is rewritten by the next call with the same arguments."""
+        arena = self._stat_arena(which)
+        tab = self.stat_table(pattern, suffix)
+        if not tab['T']:
+            return None, []                        # (nothing matches: nothing is launched)
+        return self._run_stats(arena, tab, which), tab['names']
+
+    def output_stats(self, pattern=None):
+        """The heads whose name + '_output' matches: one launch pair each through a one-segment table -> [(name + '_output', device
+        tensor (2, 8))].  Only the heads: intermediate activations live in a shared pool and many are fused away."""
+        if self.outputs is None:
+            return []
+        prog = re.compile(pattern) if pattern is not None else None
+        rows = []
+        for name, t in zip(self.sym.list_outputs(), self.outputs):
+            name = name if name.endswith('_output') else name + '_output'
+            if prog is not None and not prog.match(name):
+                continue
+            key = ('output', int(t.numel()))
+            tab = self._stat_tables.get(key)
+            if tab is None:
+                tab = self._stat_tables[key] = self._plan_stats(['output'], [(0, int(t.numel()))])
+            rows.append((name, self._run_stats(t, tab, name)))
+        return rows
+
+    def stat_views(self, pattern=None):
+        """[(monitor name, tensor)] of everything the pattern matches -- masters, '<p>_grad', '<p>_mom', then the heads -- as views,
+        for a Monitor with a stat_func of its own (the slow path)."""
+        prog = re.compile(pattern) if pattern is not None else None
+        ps = sorted((p for p in self.params.values() if p.trainable), key=lambda p: p.offset)
+        rows = []
+        for which, suffix in (('weight', ''), ('grad', '_grad'), ('mom', '_mom')):
+            arena = self._stat_arena(which)
+            rows += [(p.name + suffix, arena[p.offset:p.offset + p.numel].view(p.int_shape)) for p in ps
+                     if prog is None or prog.match(p.name + suffix)]
+        for name, t in zip(self.sym.list_outputs(), self.outputs or []):
+            name = name if name.endswith('_output') else name + '_output'
+            if prog is None or prog.match(name):
+                rows.append((name, t))
+        return rows
+
+    def set_skip_report(self, flag):
+        """flag True: whenever the guard skips a step, the per-tensor statistics of that step's gradients are left in a report buffer
+        (self.skip_report['out'], (1 + T, 8), names in self.skip_report['table']['names']): right behind the guard one
+        sn_tensor_stats(only_if_skipped = 1) rides in the optimizer pass, and in its captured graph; on a step that is not skipped
+        its blocks read the skip flag and return.  Needs the guard with skip_nonfinite (dynamic loss scaling implies it).  False (the
+        default): the optimizer pass is the one without it.  The captured optimizer graph is dropped and captured again."""
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError('skip_report must be a bool, got %r' % (flag,))
+        if flag and (self.guard is None or not self.guard['skip_nonfinite']):
+            raise ValueError('skip_report needs the gradient guard with skip_nonfinite (or dynamic loss scaling)')
+        self._graph_up = None
+        if not flag:
+            self.skip_report = None
+            return
+        tab = self.stat_table()
+        self.skip_report = {'table': tab, 'out': self.zeros((1 + tab['T'], 8), torch.float64)}
+
     def _update_body(self, lr=None, wd=None, momentum=None, rescale_grad=None):
         g, ls = self.guard, self.loss_scale
         grad = self.accum['arena'] if self.accum is not None else self.arena_grad
@@ -1159,6 +1279,11 @@ class Executor(object):
         elif g is not None:
             hip.call('sn_grad_guard', grad, grad.numel(), self.hyper, g['clip_global_norm'], g['skip_nonfinite'],
                      0, g['ws'], g['state'], hip.stream())
+        if self.skip_report is not None:
+            # where the non-finite values sit: every block returns at once unless the guard has just set skip (set_skip_report)
+            r = self.skip_report
+            t = r['table']
+            hip.call('sn_tensor_stats', grad, 1, t['plan'], t['n_items'], t['T'], 0, g['state'], 1, t['ws'], r['out'], hip.stream())
         for (lr_mult, wd_mult, _half), a, b in self.groups:
             if g is not None:
                 hip.call('sn_sgd_mom_update_guarded_dev', self.arena_master[a:], grad[a:], self.arena_mom[a:],

@@ -4,13 +4,14 @@ name ``mxnet`` so that the reference's files run unmodified on top."""
 import sys
 import types
 
-from . import io, metric, misc, ndarray, operator, symbol  # noqa: F401
+from . import io, metric, misc, mon, ndarray, operator, symbol  # noqa: F401
 from .misc import LRScheduler, Speedometer, do_checkpoint, module_checkpoint, save_checkpoint, load_checkpoint
 from .module import Module
 from .ndarray import Context, cpu, gpu
 
 nd = ndarray
 sym = symbol
+monitor = mon
 
 
 def _ns(name, **members):
@@ -38,7 +39,8 @@ def alias_as(name='mxnet'):
     sys.modules[name] = me
     for sub, m in (('nd', ndarray), ('ndarray', ndarray), ('sym', symbol), ('symbol', symbol), ('io', io), ('metric', metric),
                    ('mod', mod), ('module', mod), ('callback', callback), ('model', model), ('lr_scheduler', lr_scheduler),
-                   ('random', random), ('contrib', contrib), ('operator', operator), ('init', init), ('context', context)):
+                   ('random', random), ('contrib', contrib), ('operator', operator), ('init', init), ('context', context), ('mon', mon),
+                   ('monitor', mon)):
         sys.modules['%s.%s' % (name, sub)] = m
     sys.modules['%s.contrib.sym' % name] = symbol
     sys.modules['%s.contrib.symbol' % name] = symbol

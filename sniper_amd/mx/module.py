@@ -56,6 +56,7 @@ class Module(object):
         # True: the iterator yields the GLOBAL batch and every rank takes its slice (reference behaviour);
         # False: the iterator is already rank-local (bench.py: each rank owns an independent chip minibatch)
         self.slice_inputs = True
+        self.static_loss_scale = None      # a static loss scale folded into lr / wd by the caller: only the monitor's 'loss_scale' row reads it
 
     # ---- properties the reference reads
     @property
@@ -270,6 +271,7 @@ class Module(object):
                     'lr_scheduler': op.get('lr_scheduler')}
         self.opt.update(guard)
         self.opt['accumulate'] = self._accumulate_option(op)
+        self.opt['skip_report'] = self._skip_report_option(op, guard['skip_nonfinite'] or guard['loss_scale'] is not None)
         if self.opt['lr_scheduler'] is not None:
             self.opt['lr_scheduler'].base_lr = self.opt['lr']
         self.optimizer_initialized = True
@@ -296,6 +298,22 @@ class Module(object):
         except ValueError:
             raise ValueError('SNIPER_ACCUMULATE must be an int >= 1, got %r' % (env,))
         return Executor.check_accumulate(k)
+
+    # ---- skip report (Executor.set_skip_report): optimizer parameter skip_report; without the key, SNIPER_SKIP_REPORT=1 turns it on
+    # for the reference's unchanged main_train.py.  The key wins over the variable.
+    @staticmethod
+    def _skip_report_option(op, skips):
+        v = op.get('skip_report')
+        if v is None:
+            env = (os.environ.get('SNIPER_SKIP_REPORT') or '').strip()
+            if env not in ('', '0', '1'):
+                raise ValueError('SNIPER_SKIP_REPORT must be 0 or 1, got %r' % (env,))
+            v = env == '1'
+        if not isinstance(v, (bool, np.bool_)) and v not in (0, 1):
+            raise ValueError('optimizer parameter skip_report must be a bool, got %r' % (v,))
+        if v and not skips:
+            raise ValueError('skip_report needs skip_nonfinite (or dynamic_loss_scale): the report describes a skipped step')
+        return bool(v)
 
     def _accum_exe(self, ex):
         """the optimizer's accumulate option -> a training executor (where _guard_exe is called); k = 1 on an executor that does not
@@ -386,6 +404,8 @@ class Module(object):
             if resume is not None:                      # load_optimizer_states: go on at the checkpoint's scale
                 ex.loss_scale['state'][0] = float(resume[0])
                 ex.loss_scale['state'][2] = float(resume[1])
+        if opt.get('skip_report') or getattr(ex, 'skip_report', None) is not None:
+            ex.set_skip_report(bool(opt.get('skip_report')))
 
     _LOSS_SCALE_KEYS = ('scale', 'scale_used', 'clean', 'growths', 'backoffs', 'held_max', 'held_min')
 
@@ -459,16 +479,24 @@ class Module(object):
         g = self.exe.guard
         ls = self.exe.loss_scale
         nd_ = 16 if ls is not None else 8              # with dynamic loss scaling the scaler's eight doubles ride behind the guard's
+        rep = getattr(self.exe, 'skip_report', None)
+        nrep = rep['out'].numel() if rep is not None else 0
         host = getattr(self, '_guard_host', None)
-        if host is not None and host['slots'][0]['host'].numel() != nd_:
+        if host is not None and (host['slots'][0]['host'].numel() != nd_ or host['nrep'] != nrep):
             host = None
         if host is None:
             host = self._guard_host = {
                 'stream': torch.cuda.Stream(device=self._device), 'k': 0, 'last': None, 'skipped': 0, 'steps': 0,
-                'growths': 0, 'backoffs': 0,
+                'growths': 0, 'backoffs': 0, 'nrep': nrep, 'report': None,
                 'slots': [{'dev': torch.zeros(nd_, dtype=torch.float64, device=g['state'].device),
                            'host': torch.zeros(nd_, dtype=torch.float64, pin_memory=True),
                            'event': None, 'fresh': False} for _ in range(2)]}
+            if nrep:
+                # the skip report rides with the state: cloned on the step's stream BETWEEN two optimizer passes, so a clone is the
+                # report of one step, whole, and its header names that step
+                for slot in host['slots']:
+                    slot['rep_dev'] = torch.zeros_like(rep['out'])
+                    slot['rep_host'] = torch.zeros(tuple(rep['out'].shape), dtype=torch.float64, pin_memory=True)
         self._guard_poll(host)                                 # (before the older slot is reused)
         slot = host['slots'][host['k'] & 1]
         host['k'] += 1
@@ -480,12 +508,16 @@ class Module(object):
             slot['dev'][8:].copy_(ls['state'])
         else:
             slot['dev'].copy_(g['state'])
+        if nrep:
+            slot['rep_dev'].copy_(rep['out'])
         cloned = torch.cuda.Event()
         cloned.record(main)
         side = host['stream']
         side.wait_event(cloned)
         with torch.cuda.stream(side):
             slot['host'].copy_(slot['dev'], non_blocking=True)
+            if nrep:
+                slot['rep_host'].copy_(slot['rep_dev'], non_blocking=True)
             slot['event'] = torch.cuda.Event()
             slot['event'].record(side)
         slot['fresh'] = True
@@ -502,6 +534,7 @@ class Module(object):
                 if s[2]:
                     self.logger.warning('gradient guard: step %d skipped, %d non-finite gradient elements, norm of the finite rest %g '
                                         '(%d skipped of %d steps, %d in a row)', int(s[4]), int(s[3]), s[0], int(s[5]), int(s[4]), int(s[6]))
+                    self._skip_report_log(host, slot, s)
                 else:
                     self.logger.warning('gradient guard: %d of %d steps skipped so far', int(s[5]), int(s[4]))
             if len(s) >= 16:
@@ -510,6 +543,77 @@ class Module(object):
             if limit is not None and s[6] >= limit:
                 raise FloatingPointError('gradient guard: %d consecutive steps skipped for non-finite gradients (step %d, %d non-finite '
                                          'elements in the last one); max_consecutive_skips = %d' % (int(s[6]), int(s[4]), int(s[3]), limit))
+
+    def _skip_report_log(self, host, slot, s):
+        """the landed snapshot of a skipped step: its report (the header names this very step, or nothing is said) is kept for
+        skip_report(wait=False) and up to three of its tensors are named in a second warning"""
+        if 'rep_host' not in slot:
+            return
+        out = slot['rep_host'].numpy().copy()
+        if out[0, 0] != 1.0 or out[0, 1] != s[4]:
+            return
+        host['report'] = out
+        bad = self._report_dict(out, self.exe.skip_report['table']['names'])['tensors']
+        text = ', '.join('%s (%d of %d, first at %d)' % (t['name'], t['nonfinite'], t['numel'], t['first_index']) for t in bad[:3])
+        self.logger.warning('gradient guard: step %d skipped, non-finite gradients in %d tensors, first in %s%s', int(s[4]), len(bad), text,
+                            ', ...' if len(bad) > 3 else '')
+
+    @staticmethod
+    def _report_dict(out, names):
+        tensors = [{'name': name, 'nonfinite': int(r[2]), 'first_index': int(r[3]), 'max_abs': float(r[4]), 'norm': float(np.sqrt(r[0])),
+                    'zeros': int(r[5]), 'numel': int(r[6])} for name, r in zip(names, out[1:]) if r[2] > 0]
+        return {'step': int(out[0, 1]), 'tensors': tensors}
+
+    def skip_report(self, wait=True):
+        """Where the most recent skipped step had its non-finite gradients: {'step': the guard's step counter of that step,
+        'tensors': [{'name', 'nonfinite', 'first_index', 'max_abs', 'norm', 'zeros', 'numel'}, ...]} -- the tensors with
+        nonfinite > 0 only, in arena order; max_abs, norm and zeros describe the tensor's FINITE elements, in the arena's units (scaled
+        with a loss scale).  first_index is an index into the arena's internal layout of the parameter (a convolution weight is stored
+        [out][taps][in]), not into the reference-shaped array.  None when the report is off (optimizer parameter skip_report,
+        TRAIN.SKIP_REPORT, SNIPER_SKIP_REPORT=1) or no step has been skipped yet.  wait=True reads the device now (waits for the steps
+        enqueued so far); wait=False returns the newest report that has already landed on the host beside the guard's snapshots.
+        Either way the report is one step's: it is written by that step's optimizer pass alone and read between passes."""
+        ex = getattr(self, 'exe', None)
+        rep = getattr(ex, 'skip_report', None)
+        if rep is None:
+            return None
+        if wait:
+            out = rep['out'].cpu().numpy()
+        else:
+            host = getattr(self, '_guard_host', None)
+            out = host['report'] if host is not None else None
+        if out is None or out[0, 0] != 1.0:
+            return None
+        return self._report_dict(out, rep['table']['names'])
+
+    # ---- monitor (mx.mon.Monitor)
+    def install_monitor(self, mon):
+        """mon.install on the bound training executor; with a loss scale active the monitor's rows end with ('loss_scale', value):
+        the scale the gradient rows carry."""
+        assert self.binded, 'install_monitor: bind first'
+        mon.install(self.exe)
+        if self._monitor_scale_row not in mon.extra_rows:
+            mon.extra_rows.append(self._monitor_scale_row)
+
+    def _monitor_scale_row(self):
+        ls = self.exe.loss_scale
+        if ls is not None:
+            # the optimizer pass moves the scale and leaves the one the gradients carried in [1]; inside an accumulation window no
+            # pass has run since the forward, and [0] is still the scale in use
+            st = ls['state'].cpu().tolist()
+            ran = (getattr(self, 'opt', None) or {}).get('accumulate', 1) == 1 or getattr(self, '_accum_pending', 0) == 0
+            return [('loss_scale', st[1] if ran and st[1] > 0 else st[0])]
+        static = getattr(self, 'static_loss_scale', None)
+        return [('loss_scale', float(static))] if static not in (None, 1.0) else []
+
+    @staticmethod
+    def _monitor_from_env():
+        env = os.environ.get('SNIPER_MONITOR')
+        if env is None or not env.strip():
+            return None
+        from .mon import Monitor, parse_monitor_env
+        interval, pattern = parse_monitor_env(env)
+        return Monitor(interval, pattern=pattern)
 
     def _loss_scale_log(self, host, s):
         """one landed snapshot (guard's eight doubles, then the scaler's): a back-off is a warning, a growth an info line, once each"""
@@ -757,6 +861,12 @@ class Module(object):
         self.init_params(initializer=initializer, arg_params=arg_params, aux_params=aux_params, allow_missing=allow_missing,
                          force_init=force_init)
         self.init_optimizer(kvstore=kvstore, optimizer=optimizer, optimizer_params=optimizer_params)
+        # mx.mon.Monitor: tic() before forward_backward; update(), the metric and the batch-end callbacks; then toc_print().  Without the
+        # argument SNIPER_MONITOR=<interval>[:<regex>] makes one (the reference's main_train.py passes none).
+        if monitor is None:
+            monitor = self._monitor_from_env()
+        if monitor is not None:
+            self.install_monitor(monitor)
         cbs = lambda c: c if isinstance(c, (list, tuple)) else ([c] if c is not None else [])
         for epoch in range(begin_epoch, num_epoch):
             tic = time.time()
@@ -779,6 +889,8 @@ class Module(object):
                 self._device.type == 'cuda' and hasattr(eval_metric, 'update')
             held = None
             for data_batch in train_data:
+                if monitor is not None:
+                    monitor.tic()
                 self.forward_backward(data_batch)
                 self.update()
                 if lag:
@@ -792,6 +904,8 @@ class Module(object):
                     param = BatchEndParam(epoch=epoch, nbatch=nbatch, eval_metric=eval_metric, locals=locals())     # (once per batch)
                     for cb in cbs(batch_end_callback):
                         cb(param)
+                if monitor is not None:
+                    monitor.toc_print()
                 nbatch += 1
             if held is not None:
                 self._update_metric_from(eval_metric, held)

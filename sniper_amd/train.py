@@ -35,6 +35,15 @@ def dynamic_loss_scale(cfg):
     return opt
 
 
+def monitor_from_config(cfg):
+    """TRAIN.MONITOR_INTERVAL (an int >= 1) and TRAIN.MONITOR_PATTERN (a regular expression, default '.*') -- two keys the reference's
+    configs do not have -- -> an mx.mon.Monitor, or None without an interval"""
+    interval = getattr(cfg.TRAIN, 'MONITOR_INTERVAL', None)
+    if interval is None:
+        return None
+    return mx.mon.Monitor(interval, pattern=getattr(cfg.TRAIN, 'MONITOR_PATTERN', '.*'))
+
+
 def optimizer_params(cfg, lr_scheduler=None):
     """lib/train_utils/utils.py:13-42: fp16 folds the static loss scale into lr and wd."""
     tr = cfg.TRAIN
@@ -45,6 +54,8 @@ def optimizer_params(cfg, lr_scheduler=None):
     # gradient accumulation: TRAIN.ACCUMULATE = k, one update per k batches on the sum of their gradients -- a key the reference's
     # configs do not have; absent (None) leaves the choice to SNIPER_ACCUMULATE, else 1 (Module.init_optimizer)
     guard['accumulate'] = getattr(tr, 'ACCUMULATE', None)
+    # the skip report (Module.skip_report): TRAIN.SKIP_REPORT, absent (None) leaves the choice to SNIPER_SKIP_REPORT, else off
+    guard['skip_report'] = getattr(tr, 'SKIP_REPORT', None)
     dyn = dynamic_loss_scale(cfg)
     if dyn is not None:
         # the scale lives on the device and the update divides it out again: lr and wd are the true ones, nothing is folded, and
@@ -78,11 +89,15 @@ class Trainer(object):
     batches' gradients: k x BATCH_IMAGES chips per update, summed like k data-parallel ranks -- every batch keeps its own BatchNorm
     statistics and loss normalisation, nothing is averaged, and the schedule counts the update once.  So the reference's lr,
     warmup_step and lr_step hold when k x BATCH_IMAGES equals the reference's global batch; whoever wants the mean sets
-    rescale_grad = 1 / k.  The guard and the dynamic loss scale judge the window's sum, once per window."""
+    rescale_grad = 1 / k.  The guard and the dynamic loss scale judge the window's sum, once per window.
+    `skip_report=True` (TRAIN.SKIP_REPORT; needs skip_nonfinite or dynamic_loss_scale) keeps the per-tensor statistics of every skipped
+    step's gradients: Module.skip_report names the tensors that held the non-finite values.
+    `monitor` (an mx.mon.Monitor; or TRAIN.MONITOR_INTERVAL / TRAIN.MONITOR_PATTERN) is installed on the module; step() calls its
+    tic() before the batch and toc_print() after the update."""
 
     def __init__(self, batch_images=20, n_images=64, seed=0, momentum=0.995, rank_local=True, n_proposals=0, cfg=None,
                  fix_bn=False, fixed_params=None, ohem=None, clip_gradient=None, clip_global_norm=None, skip_nonfinite=False,
-                 dynamic_loss_scale=None, accumulate=None):
+                 dynamic_loss_scale=None, accumulate=None, skip_report=False, monitor=None):
         self.cfg = cfg or cfgmod.res101_e2e(batch_images=batch_images)
         cfg = self.cfg
         if accumulate is not None:
@@ -95,6 +110,16 @@ class Trainer(object):
             cfg.TRAIN.CLIP_GLOBAL_NORM = clip_global_norm
         if skip_nonfinite:
             cfg.TRAIN.SKIP_NONFINITE = True
+        if not isinstance(skip_report, bool):
+            raise ValueError('Trainer: skip_report must be a bool, got %r' % (skip_report,))
+        if skip_report:
+            cfg.TRAIN.SKIP_REPORT = True
+        if getattr(cfg.TRAIN, 'SKIP_REPORT', None) and not (getattr(cfg.TRAIN, 'SKIP_NONFINITE', False) or
+                                                            optimizer_params(cfg).get('dynamic_loss_scale') is not None):
+            raise ValueError('Trainer: skip_report needs skip_nonfinite or dynamic_loss_scale: the report describes a skipped step')
+        if monitor is not None and not all(callable(getattr(monitor, f, None)) for f in ('install', 'tic', 'toc_print')):
+            raise ValueError('Trainer: monitor must be an mx.mon.Monitor, got %r' % (monitor,))
+        self.monitor = monitor if monitor is not None else monitor_from_config(cfg)
         if fixed_params is not None:
             cfg.network.FIXED_PARAMS = list(fixed_params)
         if ohem is not None:
@@ -117,7 +142,12 @@ class Trainer(object):
         if getattr(self.net, 'fix_bn', False):
             arg, aux = self._batch_statistics(net_cls, rank_local, arg, aux)
         self.mod.init_params(arg_params=arg, aux_params=aux, allow_missing=True)
-        self.mod.init_optimizer(optimizer='sgd', optimizer_params=optimizer_params(cfg))
+        op = optimizer_params(cfg)
+        self.mod.init_optimizer(optimizer='sgd', optimizer_params=op)
+        if cfg.TRAIN.fp16 and op.get('dynamic_loss_scale') is None:
+            self.mod.static_loss_scale = float(cfg.TRAIN.scale)       # (the monitor's 'loss_scale' row)
+        if self.monitor is not None:
+            self.mod.install_monitor(self.monitor)
         self.batch = self.iter.batch
 
     def _bind(self, net, rank_local):
@@ -154,6 +184,10 @@ class Trainer(object):
 
     def step(self, batch=None):
         b = batch if batch is not None else self.batch
+        if self.monitor is not None:
+            self.monitor.tic()
         self.mod.forward_backward(b)
         self.mod.update()
+        if self.monitor is not None:
+            self.monitor.toc_print()
         return self.mod.get_outputs()
