@@ -1211,6 +1211,25 @@ int sn_vocgt_scan(const uint64_t *obj_ptrs, const uint64_t *cls_ptrs, const int3
 int sn_vocgt_crop(const uint64_t *obj_ptrs, const int32_t *hw, const int32_t *h_hw, int I, const int32_t *rec, const int32_t *h_rec,
                      const int64_t *pool_off, const int64_t *h_pool_off, long N, uint8_t *pool, long pool_total, sn_stream_t stream);
 
+/* Box voting after the test-time NMS (TEST.BBOX_VOTE; ours, modelled on Detectron's box_utils.box_voting).
+ * Problem q = image * nc + class owns rows [d_off[q], d_off[q+1]) of BOTH arrays: d_all_rows holds the (n_a, 5) f32 rows
+ * [x1,y1,x2,y2,score] handed to the NMS (a copy taken before it, read only), d_top_rows what the NMS left in place -- its first
+ * d_top_count[q] rows are the kept boxes with their post-NMS scores; rows past the count are never read or written.
+ * sn_box_vote: every kept row t is replaced by the score-weighted mean of the rows a of d_all_rows with overlap(t, a) >= thresh
+ *   (the float64 +1-pixel overlap of lib/bbox/bbox.pyx from the float32 coordinates; weights = the PRE-NMS scores; float64 sums
+ *   added in ascending row order, divided, narrowed to float32).  A row without a voter (non-positive width or height) or with a
+ *   weight sum that is not > 0 stays untouched.  method 0 'ID': the score stays; 1 'AVG': (float)(sum s / voters); 2 'IOU_AVG':
+ *   (float)(sum iou * s / sum iou).  In place, order and counts unchanged; no atomics, no workspace, the same bits every run.
+ *   d_tiles (n_tiles, 2) i32 = {problem, first kept row} for every sn_box_vote_limits()[0] rows of every problem's PRE-NMS size (an
+ *   upper bound of its kept rows, known on the host; a tile at or beyond d_top_count[q] returns) -- no host read of the counts.
+ * sn_box_vote_limits: h_out2 (HOST) = {kept rows per tile, pre-NMS rows per LDS chunk}.
+ * Refused before any launch, by a message that names the function and the condition: NULL pointers; P < 0; n_tiles < 0; thresh
+ *   outside (0, 1] or NaN; a method other than 0 / 1 / 2; arrays not aligned to 4 bytes; d_top_rows == d_all_rows.  P == 0 or
+ *   n_tiles == 0: nothing is launched. */
+int sn_box_vote_limits(int32_t *h_out2);
+int sn_box_vote(float *d_top_rows, const float *d_all_rows, const int32_t *d_off, const int32_t *d_top_count, const int32_t *d_tiles,
+                int n_tiles, int P, double thresh, int method, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

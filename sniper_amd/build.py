@@ -41,6 +41,7 @@ EXTRA = {
     "grad_guard.hip": ["-ffp-contract=off"],      # norm, then norm + 1e-6: the state is compared bit for bit with its restatement
     "loss_scale.hip": ["-ffp-contract=off"],      # the same finalize with the scale divided out, and the scale policy: bit-compared too
     "tensor_stats.hip": ["-ffp-contract=off"],    # per-tensor records, compared bit for bit with their restatement
+    "box_vote.hip": ["-ffp-contract=off"],        # box_overlap.h, and float64 sums compared bit for bit with their restatement
 }
 BASE = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
         "-Rpass-analysis=kernel-resource-usage"]

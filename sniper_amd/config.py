@@ -71,6 +71,9 @@ def _base():
         'BATCH_IMAGES': (2, 2, 4), 'RPN_NMS_THRESH': 0.7, 'RPN_PRE_NMS_TOP_N': 6000, 'RPN_POST_NMS_TOP_N': 300,
         'RPN_MIN_SIZE': 0, 'NMS': -1, 'NMS_SIGMA': 0.55, 'MAX_PER_IMAGE': 200, 'AUTO_FOCUS': False,
         'DO_PRUNING': (False, False, False), 'CHIP_HYPERPARAMS': ((-1, -1, -1),) * 3, 'CONCURRENT_JOBS': 1,
+        # box voting between the NMS and MAX_PER_IMAGE (ours, after Detectron's TEST.BBOX_VOTE; ext/box_vote.py): off by default.
+        # BBOX_VOTE_SCORING: 'ID' (scores stay), 'AVG' or 'IOU_AVG'
+        'BBOX_VOTE': False, 'BBOX_VOTE_TH': 0.8, 'BBOX_VOTE_SCORING': 'ID',
     }
     return c
 

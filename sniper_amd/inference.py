@@ -22,6 +22,7 @@ import sniper_amd.mx as mx
 
 from . import hip
 from .chips_inference import add_chips
+from .ext import box_vote as _box_vote
 from .ext import cpu_nms as _cpu_nms
 from .ext import gpu_nms as _gpu_nms
 from .iterators.MNIteratorTestAutoFocus import MNIteratorTestAutoFocus
@@ -306,6 +307,7 @@ class Tester(object):
         self.num_images = len(roidb)
         self.imdb_name = getattr(imdb, 'name', 'imdb')
         self.nms_worker = nms_worker(cfg.TEST.NMS, cfg.TEST.NMS_SIGMA)
+        self._vote_opts = _box_vote.vote_options(cfg.TEST)      # a bad threshold or method fails here, not after the forward passes
         self.batch_size = batch_size or self.cfg.TEST.BATCH_IMAGES
         self.roidb = roidb
         self.verbose = len(roidb) > 1
@@ -520,11 +522,34 @@ class Tester(object):
                             np.asarray(self.cfg.network.PIXEL_MEANS, np.float32)[[2, 1, 0]], 0.5)
         _save_all(pics, [os.path.join(out_dir, file_of(i) + vis_ext) for i in range(len(pics))], self._vis_encoder())
 
+    def _bbox_vote(self):
+        """cfg.TEST.BBOX_VOTE (+ _TH, _SCORING) or SNIPER_BBOX_VOTE=<thresh>[:<method>] -> None or (thresh, method): box voting
+        between the NMS and the MAX_PER_IMAGE rule (ext/box_vote.py).  Read and validated once, when the Tester is built."""
+        return self._vote_opts
+
+    @staticmethod
+    def _vote_host(final, rows, sizes, vote):
+        """Box voting for the host statement: `final` = the NMS output per problem, `rows` / `sizes` = the stacked problems it
+        was handed.  The kept rows go back into their problem's slots and the one device operator runs on them."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 5)
+        sizes = np.asarray(sizes, np.int64).reshape(-1)
+        off = np.concatenate(([0], np.cumsum(sizes))).tolist()
+        top = np.zeros_like(rows)
+        counts = np.fromiter((len(f) for f in final), np.int32, len(final))
+        for q, f in enumerate(final):
+            if len(f):
+                top[off[q]:off[q] + len(f)] = f
+        voted = _box_vote.box_vote_stacked(top, counts, rows, sizes, vote[0], vote[1])
+        return [voted[off[q]:off[q] + int(counts[q])] for q in range(len(final))]
+
     def _aggregate_host(self, scale_cls_dets):
         all_boxes = [[[] for _ in range(self.num_images)] for _ in range(self.num_classes)]
         # one batched launch instead of Pool(32).map; the problems go up as the one stacked array they are built as
         rows, sizes = aggregate_problems(scale_cls_dets, self.cfg.TEST.VALID_RANGES, self.num_images, self.num_classes, stacked=True)
         final = self.nms_worker.nms_wrapper.process_stacked(rows, sizes)
+        vote = self._bbox_vote()
+        if vote is not None:
+            final = self._vote_host(final, rows, sizes, vote)
         k = 0
         for i in range(self.num_images):
             for j in range(1, self.num_classes):
@@ -596,8 +621,12 @@ class Tester(object):
         cnt = torch.empty((n_img * nc,), dtype=torch.int32, device=rows.device)
         from .ext.cpu_nms import _soft_ws
         max_n = int(sizes.max())
+        vote = self._bbox_vote()
+        pre_nms = rows.clone() if vote is not None else None          # the soft-NMS works in place: the voters are its input
         hip.call('sn_soft_nms_batch', rows, d_off, n_img * nc, max_n, total, float(nms.sigma), 0.3, 0.001, 2,
                  _soft_ws(max_n, total, rows.device), cnt, hip.stream())
+        if vote is not None:
+            _box_vote.box_vote_stacked(rows, cnt, pre_nms, sizes.ravel(), vote[0], vote[1], d_off=d_off)
         if self.cfg.TEST.MAX_PER_IMAGE > 0:
             hip.call('sn_det_cap_per_image', rows, d_off, cnt, n_img, nc, int(self.cfg.TEST.MAX_PER_IMAGE), hip.stream())
         h, c = rows.cpu().numpy(), cnt.cpu().numpy()
